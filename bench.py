@@ -24,7 +24,15 @@ h2h     : the same steps timed host to host as well (tokens / reference / noise 
           reported beside `value`, which the driver contract fixes as device-resident (inputs in HBM when the
           timed region starts; the PCIe-inclusive rate is never `value`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: starts N rank processes itself)
+plain   : a plain run sets up, warms up, times the K steps and prints the line: value, ms_per_step and the
+          configuration.  Everything else above (latency, roofline, cpu, h2h, and the long-form and precise modes)
+          takes runs of its own and is measured only with --full; without it the line holds null for those keys.
+dump    : --dump-outputs DIR writes what the last timed step computed (wav, codes, F0, N of the whole batch, read from
+          the timed schedule's own output buffers) as float32 DIR/<name>.npy; inputs and weights are seeded, so two
+          builds can be compared array by array.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                               (N > 1: starts N rank processes itself)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -54,6 +62,7 @@ STEPS_LATENCY = 10
 CHUNK_HALO = 10   # configs[4] chunked decoder: aligned frames of context each side of a 1-s chunk
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md; no sparsity)
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 60_000_000     # --dump-outputs: at most this much in all (under 64 MB with the .npy headers)
 
 
 def make_inputs(S, B, seed):
@@ -223,6 +232,37 @@ def _family(w, shp):
     return "other convs (k>1)"
 
 
+def dominant_roofline(eng, step):
+    """roofline of the dominant kernel: one instrumented eager pass of `step`, events on the kernel's stream."""
+    gpu_ahead()
+    eng.start_timer({"rb.c1", "rb.c2"})
+    step()
+    rec = eng.stop_timer()
+    tsum = sum(r[1] for r in rec)
+    fsum = sum(r[2] for r in rec)
+    bsum = sum(r[3] for r in rec)
+    nl = max(len(rec), 1)
+    achieved = (fsum / nl) / (tsum / nl) / 1e12 if tsum > 0 else 0.0
+    # SURVEY.md §8(d): per launch t_roof = max(F / P_mfma, B_alg / BW_hbm); aggregate = sum t_roof / sum t_meas
+    # (the k3 convs are HBM-bound at 128 channels, the k7 / k11 ones MFMA-bound)
+    t_roof = sum(max(r[2] / (PEAK_BF16_TFLOPS * 1e12), r[3] / (PEAK_HBM_GBS * 1e9)) for r in rec)
+    n_hbm = sum(1 for r in rec if r[3] / (PEAK_HBM_GBS * 1e9) > r[2] / (PEAK_BF16_TFLOPS * 1e12))
+    # HBM bytes per launch from the committed PMC passes of this workload (tools/pmc_bench.sh)
+    traffic, tsrc = None, None
+    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_mrf.json")))
+    if pmcs:  # the newest round's PMC passes (tools/pmc_bench.sh)
+        with open(pmcs[-1]) as f:
+            traffic, tsrc = json.load(f).get("traffic_bytes_per_launch"), "profiles/" + os.path.basename(pmcs[-1])
+    return dict(bound="mfma", achieved=round(achieved, 2), peak=PEAK_BF16_TFLOPS, unit="TFLOP/s",
+                frac=round(achieved / PEAK_BF16_TFLOPS, 4), traffic=traffic, traffic_src=tsrc,
+                alg_bytes_per_launch=round(bsum / nl),
+                kernel="generator MRF convs: mrfv_conv (csrc/mrfv.hip; stage 1 narrow, stage 0 the wide 256-channel form)",
+                launches=len(rec),
+                avg_launch_us=round(tsum / nl * 1e6, 2), alg_gflop_per_launch=round(fsum / nl / 1e9, 3),
+                time_frac=round(t_roof / tsum, 4) if tsum > 0 else None, hbm_bound_launches=n_hbm,
+                alg_hbm_gbs=round(bsum / tsum / 1e9, 1) if tsum > 0 else None)
+
+
 def stage_roofline(eng, S, tok_d, ref_d, eps_d, dur_d, seeds, n_frames):
     """SURVEY.md §8(d) per stage: sum t_roof / sum t_meas, one eager pass of the bench workload (batch B on one
     stream, enqueued behind gpu_ahead()).  t_meas = the stage's span between HIP events on the launching stream;
@@ -358,15 +398,17 @@ def shard_runner(eng, S, dev, tok_d, ref_d, eps_d, dur_d, seeds, n_frames, nstre
     Host-to-host steps (h2h=True): per shard one H2D and one D2H copy stream, ordered by events so the copies overlap
     the shard's other phase -- step i+1's inputs go in once step i's front graph has read them (during its back graph),
     step i's waveform comes out during step i+1's front graph, and back graph i+1 waits for that D2H.
-    -> (run_steps(k, h2h=False), twins, host buffers {tok, ref, eps, dur, wav} (pinned))"""
+    -> (run_steps(k, h2h=False), twins, host buffers {tok, ref, eps, dur, wav} (pinned));
+    run_steps.outputs() -> the last step's device outputs {wav, codes, F0, N} (--dump-outputs)"""
     B = tok_d.shape[0]
     sizes = [B // nstream + (1 if i < B % nstream else 0) for i in range(nstream)]
-    pairs, twins = [], []
+    pairs, twins, states = [], [], []
     for i in range(nstream):
         tw = eng.twin()
         twins.append(tw)
         sl = slice(sum(sizes[:i]), sum(sizes[:i + 1]))
         st_ = {}
+        states.append(st_)
 
         def front(tw=tw, sl=sl, st_=st_):
             h, pr = tw.encode_inputs(tok_d[sl], ref_d[sl], pidx)
@@ -434,6 +476,11 @@ def shard_runner(eng, S, dev, tok_d, ref_d, eps_d, dur_d, seeds, n_frames, nstre
                         out_done[j].record(d2h_streams[j])
         for st in streams + (h2d_streams + d2h_streams if h2h else []):
             cur.wait_stream(st)
+    # every step rewrites the same graph buffers: the shards' outputs, in utterance order
+    run_steps.outputs = lambda: dict(wav=torch.cat([p[3] for p in pairs]),
+                                     codes=torch.cat([s["codes"] for s in states]),
+                                     F0=torch.cat([s["pro"]["F0"] for s in states]),
+                                     N=torch.cat([s["pro"]["N"] for s in states]))
     return run_steps, twins, host
 
 
@@ -448,7 +495,8 @@ def pipe_runner(eng, S, dev, tok_d, ref_d, eps_d, dur_d, seeds, n_frames, pidx, 
     stream before each front, each back shard's waveform comes out on its stream after it.
     The front ends at the prosody: moving the decoder pre-blocks + harmonic source into it measured slower (18.3k vs
     19.2k audio-s/s), the harmonic source alone flat (profiles/r06y, r06z).
-    -> (run_steps(k, h2h=False), twins, host buffers {tok, ref, eps, dur, wav} (pinned))"""
+    -> (run_steps(k, h2h=False), twins, host buffers {tok, ref, eps, dur, wav} (pinned));
+    run_steps.outputs() -> the last step's device outputs {wav, codes, F0, N} (--dump-outputs)"""
     B = tok_d.shape[0]
     sizes = [B // nback + (1 if i < B % nback else 0) for i in range(nback)]
     offs = [sum(sizes[:j]) for j in range(nback)]
@@ -482,10 +530,14 @@ def pipe_runner(eng, S, dev, tok_d, ref_d, eps_d, dur_d, seeds, n_frames, pidx, 
     host = dict(zip(("tok", "ref", "eps", "dur"), (t.pin_memory() for t in host_src)))
     host["wav"] = torch.empty(B, nwav, dtype=torch.float32).pin_memory()
 
+    last = [0]  # twin set (step parity) of the last step run
+
     def run_steps(k, h2h=False):
         cur = torch.cuda.current_stream(dev)
         for x in [sF] + sD:
             x.wait_stream(cur)
+        if k > 0:
+            last[0] = (k - 1) & 1
         fdone = [torch.cuda.Event() for _ in range(k)]
         bdone = [[torch.cuda.Event() for _ in range(nback)] for _ in range(k)]
         for i in range(k):
@@ -508,6 +560,8 @@ def pipe_runner(eng, S, dev, tok_d, ref_d, eps_d, dur_d, seeds, n_frames, pidx, 
                     bdone[i][j].record(sD[j])
         for x in [sF] + sD:
             cur.wait_stream(x)
+    run_steps.outputs = lambda: dict(wav=torch.cat([b[1] for b in graphs[last[0]][1]]), codes=st[last[0]]["codes"],
+                                     F0=st[last[0]]["pro"]["F0"], N=st[last[0]]["pro"]["N"])
     return run_steps, fr + twins, host
 
 
@@ -579,6 +633,23 @@ def dry_run(world, rank):
         dist.destroy_process_group()
 
 
+def dump_outputs(out_dir, outs, rank=0, budget=DUMP_BYTES):
+    """--dump-outputs: every array of `outs` as float32 <out_dir>/<name>.npy (ranks > 0: <name>.rank<r>.npy).  If the
+    arrays exceed `budget` bytes in all, each array above its equal share is cut down to a fixed sample of its
+    flattened elements (sorted indices drawn without replacement from numpy's default_rng(0): the same elements in
+    every run and every build)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in outs.items()}
+    if sum(a.nbytes for a in arrs.values()) > budget:
+        share = budget // len(arrs) // 4
+        for k, a in arrs.items():
+            if a.size > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+                arrs[k] = a.reshape(-1)[idx]
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -589,12 +660,20 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=B_THROUGHPUT)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the host-to-host steps, "
+                         "the roofline passes, the configs[1] latency, the long-form and precise modes and the CPU "
+                         "baseline (each can be dropped again with its --no-... flag); without it the line holds null "
+                         "for them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (wav, codes, F0, N of the whole "
+                         "batch) as float32 DIR/<name>.npy; the inputs are seeded, so two builds compare array by array")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-longform", action="store_true")
-    ap.add_argument("--no-precise", action="store_true")
-    ap.add_argument("--no-stages", action="store_true", help="skip the per-stage roofline pass")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the configs[1] latency leg")
+    ap.add_argument("--no-longform", action="store_true", help="--full without the configs[4] long-form leg")
+    ap.add_argument("--no-precise", action="store_true", help="--full without the precise-mode leg")
+    ap.add_argument("--no-stages", action="store_true", help="--full without the per-stage roofline pass")
     ap.add_argument("--streams", type=int, default=4,
                     help="split the per-GPU batch over this many concurrently replayed graphs (engine twins)")
     ap.add_argument("--schedule", choices=("shards", "pipe"), default="pipe",
@@ -613,6 +692,8 @@ def main():
                          "discrete codes (stzs.dist.broadcast_prompt_codes); every step then skips the prompt front "
                          "end (reported in config; off by default: each utterance has its own reference)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"[bench] --steps {args.steps} --warmup {args.warmup}: need at least one timed step")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
@@ -652,7 +733,8 @@ def main():
     bsv = args.branch_streams
     bs = (bsv == "1") if bsv in ("0", "1") else frozenset(v for v in bsv.split(",") if v)
     eng = StyleTTSZS(S, None, device=dev, packed=W, branch_streams=bs)
-    P = init_params(S, seed=0) if rank == 0 and world == 1 else None  # host params: CPU baseline / extra modes
+    # host params: CPU baseline / extra modes (--full)
+    P = init_params(S, seed=0) if args.full and rank == 0 and world == 1 else None
 
     B = args.batch
     tok, ref, eps, dur, seeds = rank_inputs(S, B, rank)
@@ -698,6 +780,7 @@ def main():
         twins += tws
     else:
         host = {}
+        cur_out = [out]  # the graph's output buffers, or the last eager step's
 
         def run_steps(k, h2h=False):
             for _ in range(k):
@@ -705,9 +788,12 @@ def main():
                     for d_, h_ in ((tok_d, host["tok"]), (ref_d, host["ref"]), (eps_d, host["eps"]),
                                    (dur_d, host["dur"])):
                         d_.copy_(h_, non_blocking=True)
-                run()
+                o = run()
+                if graph is None:
+                    cur_out[0] = o
                 if h2h:
-                    host["wav"].copy_(out["wav"], non_blocking=True)
+                    host["wav"].copy_(cur_out[0]["wav"], non_blocking=True)
+        run_steps.outputs = lambda: {k: cur_out[0][k] for k in ("wav", "codes", "F0", "N")}
     run_steps(args.warmup)
     torch.cuda.synchronize()
     if world > 1:
@@ -719,60 +805,43 @@ def main():
     if world > 1:
         dist.barrier()
     el = time.perf_counter() - t0
-    # the same steps host to host (inputs from pinned host memory, waveform back): reported beside `value`
-    if not host:
-        host.update(zip(("tok", "ref", "eps", "dur"), (t.pin_memory() for t in (tok, ref, eps, dur))))
-        host["wav"] = torch.empty(B, out["wav"].shape[1], dtype=torch.float32).pin_memory()
-    run_steps(1, h2h=True)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    run_steps(args.steps, h2h=True)
-    torch.cuda.synchronize()
-    el_h2h = time.perf_counter() - t1
+    if args.dump_outputs:  # what the last timed step left in the schedule's output buffers
+        dump_outputs(args.dump_outputs, run_steps.outputs(), rank)
+    # --full: the same steps host to host (inputs from pinned host memory, waveform back): reported beside `value`
+    el_h2h = None
+    if args.full:
+        if not host:
+            host.update(zip(("tok", "ref", "eps", "dur"), (t.pin_memory() for t in (tok, ref, eps, dur))))
+            host["wav"] = torch.empty(B, out["wav"].shape[1], dtype=torch.float32).pin_memory()
+        run_steps(1, h2h=True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run_steps(args.steps, h2h=True)
+        torch.cuda.synchronize()
+        el_h2h = time.perf_counter() - t1
     h2d_bytes = sum(t.numel() * t.element_size() for t in (tok, ref, eps, dur))
     if world > 1:
         from stzs.dist import reduce_max
-        el, el_h2h = reduce_max([el, el_h2h], dev)
+        if args.full:
+            el, el_h2h = reduce_max([el, el_h2h], dev)
+        else:
+            el = reduce_max([el], dev)[0]
     total_audio = world * B * audio_s * args.steps
     value = total_audio / el  # whole job: every rank's utterances over the slowest rank's clock
     # the LSTM exchange's spin-timeout words of every engine that ran (a timeout = wrong prosody, reported);
     # the latency / long-form / precise engines are added below
     lstm_timeouts = sum(1 for tw in twins if int(tw.status.item()) != 0)
 
-    # ---- roofline of the dominant kernel: instrumented eager pass, events on the kernel's stream ----
-    gpu_ahead()
-    eng.start_timer({"rb.c1", "rb.c2"})
-    step()
-    rec = eng.stop_timer()
-    tsum = sum(r[1] for r in rec)
-    fsum = sum(r[2] for r in rec)
-    bsum = sum(r[3] for r in rec)
-    nl = max(len(rec), 1)
-    achieved = (fsum / nl) / (tsum / nl) / 1e12 if tsum > 0 else 0.0
-    # per launch t_roof = max(F / P_mfma, B_alg / BW_hbm); aggregate = sum t_roof / sum t_meas
-    # (the k3 convs are HBM-bound at 128 channels, the k7 / k11 ones MFMA-bound)
-    t_roof = sum(max(r[2] / (PEAK_BF16_TFLOPS * 1e12), r[3] / (PEAK_HBM_GBS * 1e9)) for r in rec)
-    n_hbm = sum(1 for r in rec if r[3] / (PEAK_HBM_GBS * 1e9) > r[2] / (PEAK_BF16_TFLOPS * 1e12))
-    # HBM bytes per launch from the committed PMC passes of this workload (tools/pmc_bench.sh)
-    traffic, tsrc = None, None
-    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_mrf.json")))
-    if pmcs:  # the newest round's PMC passes (tools/pmc_bench.sh)
-        with open(pmcs[-1]) as f:
-            traffic, tsrc = json.load(f).get("traffic_bytes_per_launch"), "profiles/" + os.path.basename(pmcs[-1])
-    roof = dict(bound="mfma", achieved=round(achieved, 2), peak=PEAK_BF16_TFLOPS, unit="TFLOP/s",
-                frac=round(achieved / PEAK_BF16_TFLOPS, 4), traffic=traffic, traffic_src=tsrc,
-                alg_bytes_per_launch=round(bsum / nl),
-                kernel="generator MRF convs: mrfv_conv (csrc/mrfv.hip; stage 1 narrow, stage 0 the wide 256-channel form)",
-                launches=len(rec),
-                avg_launch_us=round(tsum / nl * 1e6, 2), alg_gflop_per_launch=round(fsum / nl / 1e9, 3),
-                time_frac=round(t_roof / tsum, 4) if tsum > 0 else None, hbm_bound_launches=n_hbm,
-                alg_hbm_gbs=round(bsum / tsum / 1e9, 1) if tsum > 0 else None)
-    if not args.no_stages:  # SURVEY.md §8(d) aggregate per stage (sum t_roof / sum t_meas) + per kernel family
-        roof["stages"] = stage_roofline(eng, S, tok_d, ref_d, eps_d, dur_d, seeds, n_frames)
+    # everything below measures beside the headline and takes runs of its own: --full only
+    roof = None
+    if args.full:
+        roof = dominant_roofline(eng, step)
+        if not args.no_stages:  # SURVEY.md §8(d) aggregate per stage (sum t_roof / sum t_meas) + per kernel family
+            roof["stages"] = stage_roofline(eng, S, tok_d, ref_d, eps_d, dur_d, seeds, n_frames)
 
     # ---- p50 latency, configs[1]: batch 1, 10-step CFG-5 ----
     lat = None
-    if not args.no_latency:
+    if args.full and not args.no_latency:
         # host to host, as the metric defines the latency: tokens / reference / noise / durations
         # copied in from pinned host memory, the graph replayed, the waveform copied back, then a synchronize
         host1 = [t.pin_memory() for t in make_inputs(S, 1, seed=1000 + rank)]
@@ -820,17 +889,17 @@ def main():
 
     # ---- configs[4]: 30-s target, batch 1, fp8 denoiser linears, streaming iSTFT (1-s chunks) ----
     lf = None
-    if not args.no_longform and world == 1:
+    if args.full and not args.no_longform and world == 1:
         lf = longform(S, P, dev)
         lstm_timeouts += lf.pop("lstm_timeouts")
     pr = None
-    if not args.no_precise and world == 1:
+    if args.full and not args.no_precise and world == 1:
         # (shards: 2 -- 4 measured slower in the fp32-activation mode, r05_j 6 491 vs 7 756)
         pr = precise_mode(S, P, dev, schedule=args.precise_schedule)
         lstm_timeouts += int(pr["lstm_status"] != 0)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(S, P)
 
     if rank == 0:
@@ -850,6 +919,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "bf16",
+            "full": bool(args.full),
             "data": "synthetic (seeded tokens 16/s, 3-s noise reference, forced [3,2] durations); random-init weights",
             "config": {"workload": "configs[2]: batch 64/GPU, 5-s targets, 2-step distilled style diffusion, CFG 5",
                        "global_batch": world * B, "seq_len": n_frames, "parallelism": f"dp{world} (utterance shards)",
@@ -863,7 +933,8 @@ def main():
             "weight_broadcast_ms": round(bcast_ms, 3),
             "rehearsal": rehearsal,
             "lstm_timeouts": lstm_timeouts,
-            "host_to_host": {"value": round(world * B * audio_s * args.steps / el_h2h, 2), "unit": "audio-s/s",
+            "host_to_host": None if el_h2h is None else
+                            {"value": round(world * B * audio_s * args.steps / el_h2h, 2), "unit": "audio-s/s",
                              "ms_per_step": round(el_h2h / args.steps * 1e3, 3), "h2d_bytes_per_step": h2d_bytes,
                              "d2h_bytes_per_step": int(host["wav"].numel() * 4),
                              "note": "inputs copied in from pinned host memory and the waveform copied back inside "

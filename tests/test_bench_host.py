@@ -23,6 +23,29 @@ def test_kernel_families():
     assert bench._family("istft", None) == "istft"
 
 
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: float32 <name>.npy per array, whole while they fit the budget; above it the large arrays are cut
+    to the same seeded sample of their elements in every run, and the small ones stay whole."""
+    import numpy as np
+    import torch
+
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = dict(wav=torch.randn(3, 1000, generator=g), codes=torch.randn(3, 5, 4, generator=g).to(torch.bfloat16))
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    wav, codes = np.load(tmp_path / "a" / "wav.npy"), np.load(tmp_path / "a" / "codes.npy")
+    assert wav.dtype == codes.dtype == np.float32
+    assert np.array_equal(wav, outs["wav"].numpy()) and np.array_equal(codes, outs["codes"].float().numpy())
+    for d in ("b", "c"):  # budget 4 000 B: 500 elements per array -> wav sampled, codes whole
+        bench.dump_outputs(str(tmp_path / d), outs, budget=4000)
+    wb, wc = np.load(tmp_path / "b" / "wav.npy"), np.load(tmp_path / "c" / "wav.npy")
+    assert wb.shape == (500,) and np.array_equal(wb, wc)
+    assert np.isin(wb, wav).all() and np.array_equal(np.load(tmp_path / "b" / "codes.npy"), codes)
+    assert wb.nbytes + codes.nbytes <= 4000
+    bench.dump_outputs(str(tmp_path / "a"), outs, rank=1)
+    assert np.array_equal(np.load(tmp_path / "a" / "wav.rank1.npy"), wav)
+
+
 def test_small_rows_rule():
     from types import SimpleNamespace
 

@@ -274,6 +274,15 @@ def test_two_shard_streams_match_eager(v0, c2, branch_streams):
     assert seq_ok and conc_ok and not bad
 
 
+def _check_dumped_outputs(run_steps, g):
+    """what `bench.py --dump-outputs` writes (run_steps.outputs(): the last step's waveform, style codes, F0 and N in
+    the schedule's own output buffers) is the eager batch, bit for bit."""
+    o = run_steps.outputs()
+    assert sorted(o) == ["F0", "N", "codes", "wav"]
+    for k, v in o.items():
+        assert torch.equal(v.cpu(), g[k]), k
+
+
 @pytest.mark.parametrize("nstream,stagger", [(2, 1), (4, 2)])
 def test_bench_shard_runner_matches_eager(v0, c2, nstream, stagger):
     """bench.shard_runner itself, as the headline line runs it: the configs[2] batch split over `nstream` twins on
@@ -294,6 +303,7 @@ def test_bench_shard_runner_matches_eager(v0, c2, nstream, stagger):
     run_steps(3, h2h=True)
     torch.cuda.synchronize()
     ok3 = torch.equal(host["wav"], g["wav"])
+    _check_dumped_outputs(run_steps, g)
     st = [tw.check_status() for tw in tws]
     print(f"{nstream} shards, stagger {stagger}: h2h x1 {ok1}, h2h x3 {ok3}, max |dwav| "
           f"{(host['wav'] - g['wav']).abs().max().item():.3e}, status {st}")
@@ -316,10 +326,12 @@ def test_bench_pipe_runner_matches_eager(v0, c2, nback):
     run_steps(1, h2h=True)
     torch.cuda.synchronize()
     ok1 = torch.equal(host["wav"], g["wav"])
+    _check_dumped_outputs(run_steps, g)  # the last step ran on the first twin set ...
     host["wav"].zero_()
     run_steps(4, h2h=True)
     torch.cuda.synchronize()
     ok4 = torch.equal(host["wav"], g["wav"])
+    _check_dumped_outputs(run_steps, g)  # ... and on the second
     st = [tw.check_status() for tw in tws]
     print(f"pipe, {nback} decoder shard(s): h2h x1 {ok1}, h2h x4 {ok4}, max |dwav| "
           f"{(host['wav'] - g['wav']).abs().max().item():.3e}, status {st}")
