@@ -21,6 +21,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
+from functools import partial
 
 import numpy as np
 import torch
@@ -66,23 +67,102 @@ def _ln_cost(a):
     return 0, a.R * a.C * (_ES[a.in_dtype] + _ES[a.out_dtype])
 
 
-def _table_env(var, default):
-    v = os.environ.get(var)
-    if v is None:
-        return dict(default)
+def _conv_cost(cw, x: "Act", y: "Act", T_out, res, acc_in, ln=None):
+    """(FLOP, bytes) of a conv launch; ln: the LayerNorm (stzs_rowln_args) fused in front of it."""
+    flops = 2.0 * y.B * T_out * (cw.ups or 1) * cw.Co * cw.Ci * cw.ks
+    if cw.wx3 is not None:  # precise mode: 3 bf16 MFMA products per fp32 product (bf16x3-equivalent FLOP)
+        flops *= 3.0
+    # algorithmic bytes: input tile once + output once (+ residual/acc reads), bf16/f32 as stored, + the
+    # weights once (bf16; e4m3 for the fp8 linears; hi + lo for the split-operand precise form)
+    wbytes = (cw.ups or 1) * cw.Co * cw.Ci * cw.ks * (1 if cw.f8 else (4 if cw.wx3 is not None else 2))
+    opnd = lambda v: v.B * v.T * v.C * v.t.element_size() if v is not None else 0
+    byt = opnd(x) + y.B * T_out * (cw.ups or 1) * cw.Co * y.t.element_size() + opnd(res) + opnd(acc_in) + wbytes
+    if ln is not None:  # the LayerNorm's input rows instead of x
+        byt += ln.R * ln.C * (4 if ln.in_dtype == L.F32 else 2) - opnd(x)
+    return flops, byt
+
+
+# conv flag bits that take a conv off the generic path (csrc/conv.hip conv_mfma): the LDS-DMA GEMM (8 =
+# STZS_CONV_A_DMA), the small-M rows form and every weight form with a kernel of its own
+_CONV_NOT_GENERIC = (8 | L.CONV_ROWS | L.CONV_W_X3 | L.CONV_W_F32 | L.CONV_W_FRAG32 | L.CONV_W_LANE16 |
+                     L.CONV_W_NARROW32 | L.CONV_W_FRAG32X3)
+
+
+def _conv_generic(flags, cw) -> bool:
+    """the conv with these flags runs on the generic path (which splits K over input-channel chunks and finalises
+    deferred prologue statistics itself)"""
+    return not (flags & _CONV_NOT_GENERIC) and not cw.f8
+
+
+def _table(v):
+    """a per-linear table knob: a dict, or its environment form -- "0" = off, or e.g. "ff2=4,o=2" """
+    if not isinstance(v, str):
+        return dict(v)
     if v.strip() in ("", "0"):
         return {}
     return {k: int(n) for k, n in (kv.split("=") for kv in v.split(","))}
 
 
-def _dn_splitk_default():
-    return _table_env("STZS_DN_SPLITK", DN_SPLITK)
+def _on(v):
+    return v != "0"
+
+
+# the per-engine knobs: (attribute, environment variable, default, parser).  A constructor argument of the attribute's
+# name takes precedence over the environment; a callable default is evaluated on the engine (after the rows above it).
+_KNOBS = (
+    ("dur_overlap", "STZS_DUR_OVERLAP", "1", lambda v: bool(int(v))),
+    # split-K of the bf16 denoiser layer linears (stzs_conv_args.splitk): a property of the weight, used at
+    # every batch size so results stay batch-invariant; {} turns it off
+    ("dn_splitk", "STZS_DN_SPLITK", DN_SPLITK, _table),
+    # small-M whole-chip form of the bf16 denoiser linears (csrc/rows.hip): {linear: K slices}; a per-engine
+    # property of the weight like dn_splitk (batch-invariant), taking precedence over it
+    ("dn_rows", "STZS_DN_ROWS", DN_ROWS, _table),
+    # split-K slices of the text-encoder convs (LATENCY_TE_SPLITK); 0 = off
+    ("te_splitk", "STZS_TE_SPLITK", TE_SPLITK, int),
+    # split-K slices of the bf16 AdaIN-block convs (LATENCY_BLK_SPLITK); 0 = the register-direct form
+    ("blk_splitk", "STZS_BLK_SPLITK", BLK_SPLITK, int),
+    # InstanceNorm statistics of <= 8 partial chunks handed to the consuming generic-path conv unfinalised
+    # (stzs_conv_args.pro_part: the prologue finalises them, bit-identical, one launch less per statistics) --
+    # the engines whose AdaIN-block convs run the generic path (blk_splitk); STZS_DEFER_STATS=0|1 overrides
+    ("defer_stats", "STZS_DEFER_STATS", lambda eng: "1" if eng.blk_splitk else "0", _on),
+    # (r06) small batches (<= 4 utterances): the generator MRF's three resblocks advanced side by side, each layer's
+    # three convs in one launch (stzs_conv1d_group, csrc/mrfv.hip mrfv_trio) -- bit-identical; STZS_MRF_TRIO=0: off
+    ("mrf_trio", "STZS_MRF_TRIO", "1", _on),
+    # (r06) the batch-1 engine (blk_splitk): the prosody predictor's F0 and N branches in lockstep, each conv pair
+    # in one launch pair (stzs_conv1d_group -> conv_mfma_pair) -- bit-identical; STZS_F0N_PAIR=0: off
+    ("f0n_pair", "STZS_F0N_PAIR", "1", _on),
+    # (r06) the denoiser layers' cross-attention K / V projections as one stacked linear; STZS_KV_FUSE=0: per layer
+    ("kv_fuse", "STZS_KV_FUSE", "1", _on),
+    # the per-utterance linears (one row per utterance or per sigma step: the sigma-embedding MLP, the pooled-
+    # prompt projection, the decoder / predictor AdaIN gamma-beta GEMMs) on the whole-chip small-M form at every
+    # batch size (a per-weight choice: batch-invariant); on the tiled GEMM they ran on 1-4 workgroups each.
+    # STZS_SMALL_ROWS=0 turns it off.
+    ("small_rows", "STZS_SMALL_ROWS", "1", _on),
+    # with the denoiser linears on the small-M rows form (dn_rows): each adaLN / affine LayerNorm fused into the
+    # one linear that reads it (stzs_ln_linear, csrc/lnrows.hip) instead of its own launch.  STZS_LN_FUSE=0: off
+    ("ln_fuse", "STZS_LN_FUSE", "1", _on),
+    # rows-form linears with K <= rows16_maxk on the 16-row register-direct form (csrc/lnrows.hip rows16: up to 16
+    # K-steps of both operands in flight, no cross-wave reduction, no K slices).  STZS_ROWS16=0: csrc/rows.hip
+    ("rows16", "STZS_ROWS16", "1", _on),
+    ("rows16_split", "STZS_ROWS16_SPLIT", "1", _on),  # (the Z-slice form: batch-1 ffn2)
+    # (unsliced up to K 512: ffn2, K 2048, as one 64-K-step chain measured no faster than rows.hip Z 4, r04_t;
+    # with its 4 slices on the split form it is, r04_x)
+    ("rows16_maxk", "STZS_ROWS16_MAXK", "512", int),
+    # the last generator stage's noise conv fused into its ConvTranspose (bf16 engines); STZS_UPS_NOISE=0: off
+    ("ups_noise_fused", "STZS_UPS_NOISE", "1", _on),
+    # the first stage's strided noise conv on super-rows of the harmonic source (register-direct kernel, bf16
+    # engines); STZS_NOISE_SUPER=0: the stride-6 conv_mfma form
+    ("noise_super", "STZS_NOISE_SUPER", "1", _on),
+    # precise mode: the FRAG32 convs (MRF, AdaIN-block k3) on the split-operand register-direct kernel
+    # (csrc/mrfx.hip) instead of the LDS-ring conv_x3; STZS_MRFX=0: conv_x3
+    ("mrfx", "STZS_MRFX", "1", _on),
+    # diagnostic conv flag bits ORed into every stzs_conv1d call (e.g. STZS_CONV_LINEAR_IDS = 128)
+    ("conv_flags", "STZS_CONV_FLAGS", "0", lambda v: int(v, 0)),
+)
 
 
 def _rup(x, m):
     return (x + m - 1) // m * m
-
-
 
 
 @dataclass
@@ -161,14 +241,16 @@ class _StatsRef:
         self.eng, self.part, self.ld, self.nch, self.T, self.B = eng, part, ld, nch, T, B
         self.mean, self.rstd, self.chunk_rows, self.done = mean, rstd, chunk_rows, False
 
+    def final_args(self, s):
+        """fill s (stzs_stats_args) for the finalise of these partials -> s"""
+        s.mean, s.rstd, s.partial = self.mean.data_ptr(), self.rstd.data_ptr(), self.part.data_ptr()
+        s.stat_bs, s.B, s.T, s.C, s.eps = self.ld, self.B, self.T, self.ld, 1e-5
+        return s
+
     def finalize(self):
         if not self.done:
-            s = L.StatsArgs()
-            s.mean, s.rstd, s.partial = self.mean.data_ptr(), self.rstd.data_ptr(), self.part.data_ptr()
-            s.stat_bs, s.B, s.T, s.C, s.eps = self.ld, self.B, self.T, self.ld, 1e-5
-            self.eng.launches += 1
-            L.check(self.eng.lib.stzs_chan_stats_final(C.byref(s), self.chunk_rows, self.eng.stream()),
-                    "chan_stats_final")
+            self.eng._raw(self.eng.lib.stzs_chan_stats_final, "chan_stats_final",
+                          C.byref(self.final_args(L.StatsArgs())), self.chunk_rows)
             self.done = True
 
     def mean_ptr(self):
@@ -251,57 +333,15 @@ class StyleTTSZS:
         self._branch = ""  # scratch-key suffix of the branch being enqueued (see fork())
         self._side = {}  # (fork depth, branch) -> side stream
         self._depth = 0  # nesting depth of fork() calls being enqueued
-        self.dur_overlap = bool(int(os.environ.get("STZS_DUR_OVERLAP", "1"))) if dur_overlap is None else \
-            bool(dur_overlap)
         self.launches = 0
         self.lstm_spin_limit = 0  # 0 = the library default; tests force tiny values
-        # split-K of the bf16 denoiser layer linears (stzs_conv_args.splitk): a property of the weight, used at
-        # every batch size so results stay batch-invariant; {} turns it off
-        self.dn_splitk = _dn_splitk_default() if dn_splitk is None else dict(dn_splitk)
-        # small-M whole-chip form of the bf16 denoiser linears (csrc/rows.hip): {linear: K slices}; a per-engine
-        # property of the weight like dn_splitk (batch-invariant), taking precedence over it
-        self.dn_rows = _table_env("STZS_DN_ROWS", DN_ROWS) if dn_rows is None else dict(dn_rows)
-        # split-K slices of the text-encoder convs (LATENCY_TE_SPLITK); 0 = off
-        self.te_splitk = int(os.environ.get("STZS_TE_SPLITK", TE_SPLITK)) if te_splitk is None else int(te_splitk)
-        # split-K slices of the bf16 AdaIN-block convs (LATENCY_BLK_SPLITK); 0 = the register-direct form
-        self.blk_splitk = int(os.environ.get("STZS_BLK_SPLITK", BLK_SPLITK)) if blk_splitk is None else int(blk_splitk)
-        # InstanceNorm statistics of <= 8 partial chunks handed to the consuming generic-path conv unfinalised
-        # (stzs_conv_args.pro_part: the prologue finalises them, bit-identical, one launch less per statistics) --
-        # the engines whose AdaIN-block convs run the generic path (blk_splitk); STZS_DEFER_STATS=0|1 overrides
-        self.defer_stats = os.environ.get("STZS_DEFER_STATS", "1" if self.blk_splitk else "0") != "0"
-        # (r06) small batches (<= 4 utterances): the generator MRF's three resblocks advanced side by side, each layer's
-        # three convs in one launch (stzs_conv1d_group, csrc/mrfv.hip mrfv_trio) -- bit-identical; STZS_MRF_TRIO=0: off
-        self.mrf_trio = os.environ.get("STZS_MRF_TRIO", "1") != "0"
-        # (r06) the batch-1 engine (blk_splitk): the prosody predictor's F0 and N branches in lockstep, each conv pair
-        # in one launch pair (stzs_conv1d_group -> conv_mfma_pair) -- bit-identical; STZS_F0N_PAIR=0: off
-        self.f0n_pair = os.environ.get("STZS_F0N_PAIR", "1") != "0"
-        # (r06) the denoiser layers' cross-attention K / V projections as one stacked linear; STZS_KV_FUSE=0: per layer
-        self.kv_fuse = os.environ.get("STZS_KV_FUSE", "1") != "0"
-        # the per-utterance linears (one row per utterance or per sigma step: the sigma-embedding MLP, the pooled-
-        # prompt projection, the decoder / predictor AdaIN gamma-beta GEMMs) on the whole-chip small-M form at every
-        # batch size (a per-weight choice: batch-invariant); on the tiled GEMM they ran on 1-4 workgroups each.
-        # STZS_SMALL_ROWS=0 turns it off.
-        self.small_rows = os.environ.get("STZS_SMALL_ROWS", "1") != "0"
-        # with the denoiser linears on the small-M rows form (dn_rows): each adaLN / affine LayerNorm fused into the
-        # one linear that reads it (stzs_ln_linear, csrc/lnrows.hip) instead of its own launch.  STZS_LN_FUSE=0: off
-        self.ln_fuse = os.environ.get("STZS_LN_FUSE", "1") != "0"
-        # rows-form linears with K <= rows16_maxk on the 16-row register-direct form (csrc/lnrows.hip rows16: up to 16
-        # K-steps of both operands in flight, no cross-wave reduction, no K slices).  STZS_ROWS16=0: csrc/rows.hip
-        self.rows16 = os.environ.get("STZS_ROWS16", "1") != "0"
-        self.rows16_split = os.environ.get("STZS_ROWS16_SPLIT", "1") != "0"  # (the Z-slice form: batch-1 ffn2)
-        # (unsliced up to K 512: ffn2, K 2048, as one 64-K-step chain measured no faster than rows.hip Z 4, r04_t;
-        # with its 4 slices on the split form it is, r04_x)
-        self.rows16_maxk = int(os.environ.get("STZS_ROWS16_MAXK", "512"))
-        # the last generator stage's noise conv fused into its ConvTranspose (bf16 engines); STZS_UPS_NOISE=0: off
-        self.ups_noise_fused = os.environ.get("STZS_UPS_NOISE", "1") != "0"
-        # the first stage's strided noise conv on super-rows of the harmonic source (register-direct kernel, bf16
-        # engines); STZS_NOISE_SUPER=0: the stride-6 conv_mfma form
-        self.noise_super = os.environ.get("STZS_NOISE_SUPER", "1") != "0"
-        # precise mode: the FRAG32 convs (MRF, AdaIN-block k3) on the split-operand register-direct kernel
-        # (csrc/mrfx.hip) instead of the LDS-ring conv_x3; STZS_MRFX=0: conv_x3
-        self.mrfx = os.environ.get("STZS_MRFX", "1") != "0"
-        # diagnostic conv flag bits ORed into every stzs_conv1d call (e.g. STZS_CONV_LINEAR_IDS = 128)
-        self.conv_flags = int(os.environ.get("STZS_CONV_FLAGS", "0"), 0)
+        given = dict(dn_splitk=dn_splitk, dn_rows=dn_rows, te_splitk=te_splitk, blk_splitk=blk_splitk,
+                     dur_overlap=dur_overlap)
+        for attr, env, default, parse in _KNOBS:
+            v = given.get(attr)
+            if v is None:
+                v = os.environ.get(env, default(self) if callable(default) else default)
+            setattr(self, attr, parse(v))
         # device status word collecting the LSTM exchange's spin-timeout flag over every launch (eager or
         # graph-replayed); check_status() reads it and raises
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -370,22 +410,34 @@ class StyleTTSZS:
         """weight reference -> device tensor (arena name, or an already-resolved tensor)."""
         return x if isinstance(x, torch.Tensor) else self.W.t(x)
 
-    def _call(self, fn, arg, what, cost=None, b=None):
-        """one library launch (b: a second struct argument, stzs_lstm_pair); cost = (algorithmic FLOP, algorithmic
-        bytes) of it, recorded with HIP events when a timer of every launch is running (start_timer("*"), the
-        per-stage roofline of bench.py)."""
+    def _call(self, fn, arg, what, cost=None, b=None, shape=None, args=None):
+        """one library launch: counted, its result checked, and timed here and nowhere else (but for _launch_group,
+        whose call returns its own launch count, and the span query of _istft_chunk, no launch).  b: a second struct
+        argument (stzs_lstm_pair); args: the whole argument list (without the stream) when it is not one or two
+        structs.  cost = (algorithmic FLOP, algorithmic bytes) of it, or a function giving them, evaluated only when
+        the launch is recorded with HIP events: a conv (shape = (ks, dil, T_out, Co)) under a timer of every launch
+        or of its tag, any other launch with a cost under a timer of every launch (start_timer("*"), the per-stage
+        roofline of bench.py)."""
         self.launches += 1
-        args = (C.byref(arg),) if b is None else (C.byref(arg), C.byref(b))
+        if args is None:
+            args = (C.byref(arg),) if b is None else (C.byref(arg), C.byref(b))
         tm = self.timer
-        if tm is not None and tm["all"] and cost is not None:
+        rec = tm is not None and ((tm["all"] or what in tm["tags"]) if shape is not None else
+                                  (tm["all"] and cost is not None))
+        if rec:
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
-            L.check(fn(*args, self.stream()), what)
-            e1.record()
-            tm["rec"].append((what, e0, e1, float(cost[0]), float(cost[1]), None, self.stage))
-            return
         L.check(fn(*args, self.stream()), what)
+        if rec:
+            e1.record()
+            # (a cost function's figures are recorded as they come, a given pair as floats)
+            flop, byt = cost() if callable(cost) else (float(cost[0]), float(cost[1]))
+            tm["rec"].append((what, e0, e1, flop, byt, shape, self.stage))
+
+    def _raw(self, fn, what, *args):
+        """a launch whose arguments are not one struct (plain pointers and sizes, a struct array): never timed"""
+        self._call(fn, None, what, args=args)
 
     # ------------------------------------------------------------------ ops
     def conv(self, cw: ConvW, x: Act, y: Act, *, T_out=None, pad=0, dil=1, stride=1, pro=None, pro_act=L.ACT_NONE,
@@ -403,19 +455,60 @@ class StyleTTSZS:
         by its last-arriving workgroups: bit-identical but slower at batch 1, removed in r04 -- DESIGN.md §5.)
         pre_ln (stzs_rowln_args): the LayerNorm whose output x is, launched before the linear -- or, on the small-M
         rows form, fused into it (stzs_ln_linear, csrc/lnrows.hip: the normalised rows never leave the chip)."""
-        W = self.W
+        a, pro_ref = self._conv_fill(cw, x, y, what, T_out=T_out, pad=pad, dil=dil, stride=stride, pro=pro,
+                                     pro_act=pro_act, pro_slope=pro_slope, pro_alpha=pro_alpha, cscale=cscale, res=res,
+                                     res_tdiv=res_tdiv, acc_in=acc_in, alpha=alpha, beta=beta, gate=gate,
+                                     gate_bs=gate_bs, epi_act=epi_act, epi_slope=epi_slope, ups_pad=ups_pad,
+                                     T_final=T_final, refl=refl, x_scale=x_scale)
+        rows = self._conv_route(a, cw, x, y, flags, rows, cscale, res, stats_key)
+        if rows > 1 or splitk > 1:
+            self._conv_splitk(a, cw, x, splitk, rows, collect, what)
+        if pro_ref is not None:
+            self._conv_stats_in(a, cw, pro_ref, pre_ln)
+        st = self._conv_stats_out(a, cw, y, stats_key, collect) if stats_key is not None else None
+        fn, args, fused = self._conv_entry(a, cw, x, res, res_tdiv, gate, pre_ln, st)
+        if collect is not None:
+            assert len(args) == 1 and pre_ln is None and post_ln is None and attn is None, what
+            collect.append(a)
+        else:
+            if pre_ln is not None and not fused:
+                self._call(self.lib.stzs_row_layernorm, pre_ln, what + ".ln", cost=_ln_cost(pre_ln))
+            # (its shape and cost model are needed only for a record)
+            rec = {} if self.timer is None else dict(
+                shape=(cw.ks, dil, a.T_out, cw.Co),
+                cost=partial(_conv_cost, cw, x, y, a.T_out, res, acc_in, pre_ln if fused else None))
+            self._call(fn, a, what, args=args, **rec)
+        if post_ln is not None:  # the LayerNorm that consumes this linear's output (stzs_rowln_args)
+            self._call(self.lib.stzs_row_layernorm, post_ln, what + ".ln", cost=_ln_cost(post_ln))
+        if attn is not None:  # the attention whose q (k, v) this linear produced
+            self.attention(*attn)
+        if st is None:
+            return y
+        slab, Cc, mean, rstd, defer, ntile = st
+        ref = _StatsRef(self, slab, Cc, ntile, a.T_out, y.B, mean, rstd, L.CONV_STAT_ROWS)
+        if not defer:
+            ref.finalize()
+            return y, (mean, rstd, Cc)
+        return y, (_StatPtr(ref, 0), _StatPtr(ref, 1), Cc)
+
+    def _conv_fill(self, cw, x, y, what, *, T_out, pad, dil, stride, pro, pro_act, pro_slope, pro_alpha, cscale, res,
+                   res_tdiv, acc_in, alpha, beta, gate, gate_bs, epi_act, epi_slope, ups_pad, T_final, refl, x_scale):
+        """conv() step 1 (conv()'s own arguments, by name): the problem as stzs_conv_args -- weight form, workspaces
+        and statistics not yet chosen
+        -> (args, the deferred statistics of the AdaIN prologue still to be resolved | None)"""
         a = L.ConvArgs()
         a.x, a.w, a.y = x.ptr, self._t(cw.w).data_ptr(), y.ptr
         a.bias = self._t(cw.b).data_ptr() if cw.b is not None else None
         a.ldx, a.bsx, a.ldy, a.bsy = x.ld, x.bs, y.ld, y.bs
-        a.B, a.T_in, a.Ci, a.Co, a.ks, a.dil, a.stride, a.pad = x.B, x.T, cw.Ci, cw.Co, cw.ks, dil, stride, pad
+        T = x.T
+        a.B, a.T_in, a.Ci, a.Co, a.ks, a.dil, a.stride, a.pad = x.B, T, cw.Ci, cw.Co, cw.ks, dil, stride, pad
         assert x.C == cw.Ci, (what, x.C, cw.Ci)
         if cw.ups:
-            a.T_out = x.T + 1
+            a.T_out = T + 1
             a.ups, a.ups_pad, a.T_final, a.refl = cw.ups, ups_pad, T_final, refl
             a.pad = 1
         else:
-            a.T_out = T_out if T_out is not None else (x.T + 2 * pad - dil * (cw.ks - 1) - 1) // stride + 1
+            a.T_out = T_out if T_out is not None else (T + 2 * pad - dil * (cw.ks - 1) - 1) // stride + 1
         a.ci_pad, a.co_pad, a.cic = cw.ci_pad, cw.co_pad, cw.cic
         a.in_dtype, a.out_dtype = x.dt, y.dt
         pro_ref = None
@@ -423,7 +516,7 @@ class StyleTTSZS:
             mean, rstd, stat_bs, gbp, gb_bs, boff = pro
             a.pro_mode = L.PRO_ADAIN
             if isinstance(mean, _StatPtr) and not mean.ref.done:
-                pro_ref = mean.ref  # (resolved below, once the path is known)
+                pro_ref = mean.ref  # (resolved by _conv_stats_in, once the path is known)
             else:
                 a.pro_mean, a.pro_rstd = mean.data_ptr(), rstd.data_ptr()
             a.stat_bs = stat_bs
@@ -442,18 +535,30 @@ class StyleTTSZS:
         if cw.f8:
             assert x.t.dtype == torch.float8_e4m3fn and x_scale is not None, what
             a.x_scale, a.w_scale = x_scale.data_ptr(), self._t(cw.wscale).data_ptr()
-        if (cw.ks == 1 and stride == 1 and pad == 0 and not cw.ups and pro is None and pro_act == L.ACT_NONE
-                and not getattr(cw, "frag32", False)  # (the 1x1 block shortcuts on the register-direct form)
-                and cscale == 1.0 and x.t.dtype in (torch.bfloat16, torch.float8_e4m3fn)
-                and x.c0 + cw.ci_pad <= x.ld and a.T_out == x.T):
-            flags |= 8  # STZS_CONV_A_DMA: every row readable over ci_pad channels -> LDS-DMA GEMM path
-        fx3_conv = (cw.ks in (3, 7, 11) and epi_act == L.ACT_NONE and gate is None and
-                    (pro_act == L.ACT_SNAKE or (cw.ks == 3 and acc_in is None) or
-                     (cw.Co <= 32 and cw.ks == 7 and pro_act == L.ACT_LEAKY and pro is None and res is None and
-                      acc_in is None and stats_key is None)))  # (the last: conv_post on the narrow form)
-        fx3_lin = (cw.ks == 1 and pad == 0 and pro is None and pro_act == L.ACT_NONE and stats_key is None and
-                   a.T_out == x.T and epi_act in (L.ACT_NONE, L.ACT_GELU, L.ACT_SILU) and res_tdiv == 1)
-        if (getattr(cw, "fx3", None) is not None and self.mrfx and x.t.dtype == torch.float32 and
+        return a, pro_ref
+
+    def _conv_route(self, a, cw, x, y, flags, rows, cscale, res, stats_key) -> int:
+        """conv() step 2: the kernel form of the filled problem a -- sets a.flags, and a.w / a.cic where the form has
+        a weight copy of its own.  rows: the K slices asked of the small-M rows form -> those it takes (0: not on it).
+        Beside a it takes what a does not hold exactly: the Acts, cscale as given (a's is rounded to fp32), and
+        whether statistics are asked for."""
+        T_out, xT, xdt = a.T_out, x.T, x.t.dtype
+        stride, pad, pro_act, epi_act, res_tdiv = a.stride, a.pad, a.pro_act, a.epi_act, a.res_tdiv  # (pad 1 with ups)
+        no_pro, no_gate, no_acc = a.pro_mode == L.PRO_NONE, not a.gate, not a.acc_in
+        bare = no_pro and pro_act == L.ACT_NONE  # no prologue
+        # a plain linear: row for row, no prologue, every row readable over ci_pad channels
+        plain = (cw.ks == 1 and stride == 1 and pad == 0 and not cw.ups and bare and x.c0 + cw.ci_pad <= x.ld and
+                 T_out == xT)
+        if (plain and not getattr(cw, "frag32", False)  # (the 1x1 block shortcuts on the register-direct form)
+                and cscale == 1.0 and xdt in (torch.bfloat16, torch.float8_e4m3fn)):
+            flags |= 8  # STZS_CONV_A_DMA: the LDS-DMA GEMM path
+        fx3_conv = (cw.ks in (3, 7, 11) and epi_act == L.ACT_NONE and no_gate and
+                    (pro_act == L.ACT_SNAKE or (cw.ks == 3 and no_acc) or
+                     (cw.Co <= 32 and cw.ks == 7 and pro_act == L.ACT_LEAKY and no_pro and res is None and
+                      no_acc and stats_key is None)))  # (the last: conv_post on the narrow form)
+        fx3_lin = (cw.ks == 1 and pad == 0 and bare and stats_key is None and
+                   T_out == xT and epi_act in (L.ACT_NONE, L.ACT_GELU, L.ACT_SILU) and res_tdiv == 1)
+        if (getattr(cw, "fx3", None) is not None and self.mrfx and xdt == torch.float32 and
                 y.t.dtype == torch.float32 and stride == 1 and not cw.ups and (fx3_conv or fx3_lin) and
                 (res is None or res.t.dtype == torch.float32) and x.ptr % 32 == 0 and y.ptr % 32 == 0):
             # precise mode, register-direct: split bf16 operands on the mrfv data movement (csrc/mrfx.hip; the linears
@@ -476,19 +581,24 @@ class StyleTTSZS:
         nk = cw.ci_pad // 32
         if rows > 0 and not (nk % (4 * rows) == 0 and nk // (4 * rows) in (1, 2, 4, 8, 16)):
             rows = 0  # (a function of K only: batch invariance holds)
-        if (rows > 0 and cw.ks == 1 and stride == 1 and pad == 0 and not cw.ups and pro is None and
-                pro_act == L.ACT_NONE and not cw.f8 and cw.wx3 is None and cw.w32 is None and stats_key is None and
-                (x.t.dtype == torch.float32 or (x.t.dtype == torch.bfloat16 and cscale == 1.0)) and
-                epi_act in (L.ACT_NONE, L.ACT_GELU, L.ACT_SILU) and
-                x.c0 + cw.ci_pad <= x.ld and a.T_out == x.T):
-            # small-M linear on the whole chip (csrc/rows.hip): 16-column tiles x K split in `rows` slices
-            a.flags = (a.flags & ~8) | L.CONV_ROWS
-            a.splitk = rows if rows > 1 else 0
+        if not (rows > 0 and plain and not cw.f8 and cw.wx3 is None and cw.w32 is None and stats_key is None and
+                (xdt == torch.float32 or (xdt == torch.bfloat16 and cscale == 1.0)) and
+                epi_act in (L.ACT_NONE, L.ACT_GELU, L.ACT_SILU)):
+            return 0
+        # small-M linear on the whole chip (csrc/rows.hip): 16-column tiles x K split in `rows` slices
+        a.flags = (a.flags & ~8) | L.CONV_ROWS
+        return rows
+
+    def _conv_splitk(self, a, cw, x, splitk, rows, collect, what):
+        """conv() step 3: the K slices of a (a.splitk) with their fp32 slabs and hand-off counters, by its form: the
+        rows form's `rows` (from _conv_route), else up to `splitk` on the LDS-DMA GEMM or the generic path."""
+        if rows > 0:
             if rows > 1:
+                a.splitk = rows
                 nb = self.lib.stzs_conv_rows_workspace(x.B * x.T, cw.Co, rows)
                 a.splitk_ws = self._scratch("rows_ws", nb // 4 + 1).data_ptr()
                 a.splitk_ctr = self._counters("rows_ctr", nb // (rows * 16)).data_ptr()
-            splitk = 0
+            return
         if a.flags & 8:  # LDS-DMA GEMM: the slices split the K-steps (a function of K only: batch invariance holds)
             splitk = min(splitk, 4)  # (gemm_glds takes 2 or 4 slices)
             while splitk > 1 and (cw.ci_pad // 32) % splitk:
@@ -502,8 +612,7 @@ class StyleTTSZS:
             assert nb > 0, (what, splitk)
             a.splitk, a.splitk_ws = splitk, self._scratch("sk_ws", nb // 4).data_ptr()
             a.splitk_ctr = self._counters("sk_ctr", nb // (splitk * 32768)).data_ptr()
-        elif (splitk > 1 and not (a.flags & (8 | L.CONV_ROWS | L.CONV_W_X3 | L.CONV_W_F32 | L.CONV_W_FRAG32 |
-                                             L.CONV_W_LANE16 | L.CONV_W_NARROW32 | L.CONV_W_FRAG32X3)) and not cw.f8):
+        elif splitk > 1 and _conv_generic(a.flags, cw):
             # conv_mfma split over input-channel chunks: one 64-KB fp32 slab per (128-row tile, slice) + a ticket
             # per tile (grid.x is at most B x ceil(T_out / 128))
             tiles = x.B * ((a.T_out + 127) // 128) * (cw.co_pad // 128)
@@ -511,30 +620,38 @@ class StyleTTSZS:
             gs = f".g{len(collect)}" if collect is not None else ""  # (a collected problem: its own slabs)
             a.splitk_ws = self._scratch("csk_ws" + gs, tiles * splitk * 16384).data_ptr()
             a.splitk_ctr = self._counters("csk_ctr" + gs, tiles).data_ptr()
-        if pro_ref is not None:
-            generic = not (a.flags & (8 | L.CONV_ROWS | L.CONV_W_X3 | L.CONV_W_F32 | L.CONV_W_FRAG32 |
-                                      L.CONV_W_LANE16 | L.CONV_W_NARROW32 | L.CONV_W_FRAG32X3)) and not cw.f8
-            if generic and pre_ln is None and pro_ref.nch <= 8:  # the prologue finalises the partials itself
-                a.pro_part, a.pro_ld, a.pro_nch, a.pro_T, a.pro_eps = pro_ref.part.data_ptr(), pro_ref.ld, pro_ref.nch, \
-                    pro_ref.T, 1e-5
-            else:
-                a.pro_mean, a.pro_rstd = pro_ref.mean_ptr(), pro_ref.rstd_ptr()
-        st = None
-        if stats_key is not None:
-            Cc = _rup(cw.Co, 8)
-            ntile = (a.T_out + L.CONV_STAT_ROWS - 1) // L.CONV_STAT_ROWS
-            defer = collect is not None or (self.defer_stats and ntile <= 8)
-            # (deferred: the partials must outlive this launch until their consumer reads them -- a slab per key)
-            slab = self._scratch("stat_slab." + stats_key, y.B * ntile * Cc * 2, 1024) if defer else self._slab(y.B * ntile * Cc * 2)
-            a.stat_part, a.stat_ld = slab.data_ptr(), Cc
-            st = (slab, Cc, self.buf(stats_key + ".m", (y.B, Cc), torch.float32),
-                  self.buf(stats_key + ".r", (y.B, Cc), torch.float32), defer, ntile)
-        tm = self.timer
-        launch = lambda: self.lib.stzs_conv1d(C.byref(a), self.stream())
-        fused = False
+
+    def _conv_stats_in(self, a, cw, pro_ref, pre_ln):
+        """conv() step 4: the AdaIN prologue's statistics when they are still partials (pro_ref, a _StatsRef)"""
+        if _conv_generic(a.flags, cw) and pre_ln is None and pro_ref.nch <= 8:
+            # the prologue finalises the partials itself
+            a.pro_part, a.pro_ld, a.pro_nch, a.pro_T, a.pro_eps = pro_ref.part.data_ptr(), pro_ref.ld, pro_ref.nch, \
+                pro_ref.T, 1e-5
+        else:
+            a.pro_mean, a.pro_rstd = pro_ref.mean_ptr(), pro_ref.rstd_ptr()
+
+    def _conv_stats_out(self, a, cw, y, stats_key, collect):
+        """conv() step 5: the slab the epilogue writes the output's statistics partials to, and their mean / rstd
+        buffers -> (slab, channels, mean, rstd, finalise deferred?, partial chunks)"""
+        Cc = _rup(cw.Co, 8)
+        ntile = (a.T_out + L.CONV_STAT_ROWS - 1) // L.CONV_STAT_ROWS
+        defer = collect is not None or (self.defer_stats and ntile <= 8)
+        # (deferred: the partials must outlive this launch until their consumer reads them -- a slab per key)
+        slab = self._scratch("stat_slab." + stats_key, y.B * ntile * Cc * 2, 1024) if defer else \
+            self._scratch("stat_slab", y.B * ntile * Cc * 2)
+        a.stat_part, a.stat_ld = slab.data_ptr(), Cc
+        return (slab, Cc, self.buf(stats_key + ".m", (y.B, Cc), torch.float32),
+                self.buf(stats_key + ".r", (y.B, Cc), torch.float32), defer, ntile)
+
+    def _conv_entry(self, a, cw, x, res, res_tdiv, gate, pre_ln, st):
+        """conv() step 6: the library entry point of a -> (function, its arguments, pre_ln fused into the launch?):
+        stzs_conv1d, or for a rows-form linear stzs_ln_linear, with the LayerNorm pre_ln in front or as the 16-row
+        form (ln = NULL)."""
+        if not (a.flags & L.CONV_ROWS):
+            return self.lib.stzs_conv1d, (C.byref(a),), False
+        nk = cw.ci_pad // 32
         if pre_ln is not None:
-            nk = cw.ci_pad // 32
-            fused = bool(a.flags & L.CONV_ROWS) and a.splitk <= 1 and res is None and gate is None and \
+            fused = a.splitk <= 1 and res is None and gate is None and \
                 st is None and pre_ln.C == cw.Ci == cw.ci_pad and nk in (4, 8, 16) and pre_ln.out_dtype == L.BF16 and \
                 pre_ln.act == L.ACT_NONE and (pre_ln.x or 0) % 16 == 0 and pre_ln.ldx % 8 == 0 and \
                 pre_ln.gdiv > 0 and pre_ln.R < (1 << 22) - 16 and \
@@ -542,60 +659,18 @@ class StyleTTSZS:
                 (not pre_ln.Bt or (pre_ln.bs % 8 == 0 and pre_ln.Bt % 32 == 0))
             # (every condition stzs_ln_linear checks, csrc/lnrows.hip: a shape it refuses takes the two launches)
             if fused:
-                launch = lambda: self.lib.stzs_ln_linear(C.byref(a), C.byref(pre_ln), self.stream())
-            else:
-                self._call(self.lib.stzs_row_layernorm, pre_ln, what + ".ln", cost=_ln_cost(pre_ln))
+                return self.lib.stzs_ln_linear, (C.byref(a), C.byref(pre_ln)), True
         # a rows-form linear on the 16-row register-direct form (stzs_ln_linear, ln = NULL): K <= rows16_maxk as one
         # sequential chain per element (its K slices dropped), or with its Z in {2, 4} slices of 4..16 K-steps
-        nk = cw.ci_pad // 32
-        r16 = (pre_ln is None and self.rows16 and bool(a.flags & L.CONV_ROWS) and st is None and
+        r16 = (pre_ln is None and self.rows16 and st is None and
                (res is None or res_tdiv == 1) and x.ptr % 16 == 0 and x.ld % 8 == 0 and x.bs % 8 == 0)
         r16_split = r16 and self.rows16_split and a.splitk in (2, 4) and nk % a.splitk == 0 and \
             nk // a.splitk in (4, 8, 16)
-        r16 = r16_split or (r16 and nk in (4, 8, 16, 32, 64) and cw.ci_pad <= self.rows16_maxk)
-        if r16:
+        if r16_split or (r16 and nk in (4, 8, 16, 32, 64) and cw.ci_pad <= self.rows16_maxk):
             if not r16_split:
                 a.splitk = 0
-            launch = lambda: self.lib.stzs_ln_linear(C.byref(a), None, self.stream())
-        if collect is not None:
-            assert not fused and not r16 and pre_ln is None and post_ln is None and attn is None, what
-            collect.append(a)
-        elif tm is not None and (tm["all"] or what in tm["tags"]):
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self.launches += 1
-            L.check(launch(), what)
-            e1.record()
-            flops = 2.0 * y.B * a.T_out * (cw.ups or 1) * cw.Co * cw.Ci * cw.ks
-            if cw.wx3 is not None:  # precise mode: 3 bf16 MFMA products per fp32 product (bf16x3-equivalent FLOP)
-                flops *= 3.0
-            # algorithmic bytes: input tile once + output once (+ residual/acc reads), bf16/f32 as stored, + the
-            # weights once (bf16; e4m3 for the fp8 linears; hi + lo for the split-operand precise form)
-            wbytes = (cw.ups or 1) * cw.Co * cw.Ci * cw.ks * (1 if cw.f8 else (4 if cw.wx3 is not None else 2))
-            opnd = lambda v: v.B * v.T * v.C * v.t.element_size() if v is not None else 0
-            byt = x.B * x.T * x.C * x.t.element_size() + y.B * a.T_out * (cw.ups or 1) * cw.Co * y.t.element_size() + \
-                opnd(res) + opnd(acc_in) + wbytes
-            if fused:  # the LayerNorm's input rows instead of x
-                byt += pre_ln.R * pre_ln.C * (4 if pre_ln.in_dtype == L.F32 else 2) - x.B * x.T * x.C * x.t.element_size()
-            tm["rec"].append((what, e0, e1, flops, byt, (cw.ks, dil, a.T_out, cw.Co), self.stage))
-        elif fused or r16:
-            self.launches += 1
-            L.check(launch(), what)
-        else:
-            self._call(self.lib.stzs_conv1d, a, what)
-        if post_ln is not None:  # the LayerNorm that consumes this linear's output (stzs_rowln_args)
-            self._call(self.lib.stzs_row_layernorm, post_ln, what + ".ln", cost=_ln_cost(post_ln))
-        if attn is not None:  # the attention whose q (k, v) this linear produced
-            self.attention(*attn)
-        if st is None:
-            return y
-        slab, Cc, mean, rstd, defer, ntile = st
-        ref = _StatsRef(self, slab, Cc, ntile, a.T_out, y.B, mean, rstd, L.CONV_STAT_ROWS)
-        if not defer:
-            ref.finalize()
-            return y, (mean, rstd, Cc)
-        return y, (_StatPtr(ref, 0), _StatPtr(ref, 1), Cc)
+            return self.lib.stzs_ln_linear, (C.byref(a), None), False
+        return self.lib.stzs_conv1d, (C.byref(a),), False
 
     def _rows_z(self, cw: ConvW) -> int:
         """1 = the whole-chip small-M form (one K slice: no hand-off state) for a per-utterance linear whose K gives
@@ -631,8 +706,10 @@ class StyleTTSZS:
             t = self._bufs[key] = torch.zeros(max(n, 4096), dtype=torch.int32, device=self.device)
         return t
 
-    def _slab(self, n):
-        return self._scratch("stat_slab", n)
+    def _fork_on(self, site) -> bool:
+        """branch_streams covers the fork site: True = every site, or a set of site names"""
+        bs = self.branch_streams
+        return bs is True or (isinstance(bs, (set, frozenset)) and site in bs)
 
     def fork(self, site, *fns):
         """run fns[0] on the current stream and fns[1:] on side streams forked from it (waits on the current
@@ -641,9 +718,7 @@ class StyleTTSZS:
         decoder pre-blocks || harmonic source).
         Forks nest: a fork inside a branch takes side streams and scratch keys of its own depth, so an inner
         branch never queues behind (or shares scratch with) an outer one.  -> outputs"""
-        on = self.branch_streams is True or (isinstance(self.branch_streams, (set, frozenset)) and
-                                             site in self.branch_streams)
-        if not on or len(fns) < 2:
+        if not self._fork_on(site) or len(fns) < 2:
             return [f() for f in fns]
         cur = torch.cuda.current_stream(self.device)
         d, outer = self._depth, self._branch
@@ -705,13 +780,10 @@ class StyleTTSZS:
 
     def rowln(self, x: Act, y: Act, *, G=None, gs=0, Bt=None, bs=0, gdiv=1, gadd=1.0, act=L.ACT_NONE, slope=0.0,
               R=None, y_scale=None, what="rowln"):
-        a = L.RowLNArgs()
-        a.y_scale = y_scale.data_ptr() if y_scale is not None else None
-        a.x, a.y, a.G, a.Bt = x.ptr, y.ptr, G, Bt
-        a.ldx, a.ldy, a.gs, a.bs = x.ld, y.ld, gs, bs
-        a.R = R if R is not None else x.B * x.T
-        a.C, a.gdiv, a.in_dtype, a.out_dtype, a.act = x.C, gdiv, x.dt, y.dt, act
-        a.gadd, a.eps, a.slope = gadd, 1e-5, slope
+        a = self._ln_args(x, y, G=G, gs=gs, Bt=Bt, bs=bs, gdiv=gdiv, gadd=gadd, y_scale=y_scale)
+        a.act, a.slope = act, slope
+        if R is not None:
+            a.R = R
         assert x.ld * x.T == x.bs and y.ld * y.T == y.bs
         self._call(self.lib.stzs_row_layernorm, a, what, cost=_ln_cost(a))
 
@@ -776,16 +848,20 @@ class StyleTTSZS:
                    x.B * x.T * (8 * lw.H * 4 + 2 * lw.H * y.t.element_size()) + 2 * 4 * lw.H * lw.H * 2)
 
     def copy2d(self, x: Act, y: Act, R, Cn, bsx=None):
+        self._copy_rows(x.ptr, x.ld, x.bs if bsx is None else bsx, y.ptr, y.ld, y.bs, y.B, R, Cn, x.dt, y.dt, "copy2d")
+
+    def _copy_rows(self, x: int, ldx: int, bsx: int, y: int, ldy: int, bsy: int, nb: int, R: int, Cn: int, dti, dto,
+                   what="copy_windows"):
+        """stzs_copy2d on raw byte addresses: nb blocks of R rows x Cn columns (source block stride bsx elements)"""
         a = L.CopyArgs()
-        a.x, a.y, a.ldx, a.bsx, a.ldy, a.bsy = x.ptr, y.ptr, x.ld, x.bs if bsx is None else bsx, y.ld, y.bs
-        a.B, a.R, a.C, a.in_dtype, a.out_dtype = y.B, R, Cn, x.dt, y.dt
-        self._call(self.lib.stzs_copy2d, a, "copy2d")
+        a.x, a.y, a.ldx, a.bsx, a.ldy, a.bsy = x, y, ldx, bsx, ldy, bsy
+        a.B, a.R, a.C, a.in_dtype, a.out_dtype = nb, R, Cn, dti, dto
+        self._call(self.lib.stzs_copy2d, a, what)
 
     def mean_rows(self, x: torch.Tensor, c0, Cn, key):
         y = self.buf(key, (x.shape[0], Cn), torch.float32)
-        self.launches += 1
-        L.check(self.lib.stzs_mean_rows(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
-                                        x.shape[1] * x.shape[2], c0, Cn, Cn, self.stream()), "mean_rows")
+        self._raw(self.lib.stzs_mean_rows, "mean_rows", x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
+                  x.shape[2], x.shape[1] * x.shape[2], c0, Cn, Cn)
         return y
 
     # ------------------------------------------------------------------ front ends
@@ -797,9 +873,8 @@ class StyleTTSZS:
         B, T = tokens.shape
         e = self.act("te.e", B, T, S.d_txt, self.adt)
         c = self.act("te.c", B, T, S.d_txt, self.adt)
-        self.launches += 1
         emb = self.lib.stzs_embed_f32 if self.adt == torch.float32 else self.lib.stzs_embed
-        L.check(emb(tokens.data_ptr(), W.t(W.te_emb).data_ptr(), e.ptr, B, T, S.d_txt, e.ld, self.stream()), "embed")
+        self._raw(emb, "embed", tokens.data_ptr(), W.t(W.te_emb).data_ptr(), e.ptr, B, T, S.d_txt, e.ld)
         for i in range(S.te_layers):
             self.conv(W.te_conv[i], e, c, pad=S.te_kernel // 2, splitk=0 if self.adt == torch.float32 else self.te_splitk,
                       what=f"te.conv{i}")
@@ -906,15 +981,12 @@ class StyleTTSZS:
         st = self.denoiser_prepare(h_txt, prompt, sig[:steps], cfg)
         x = self.buf("dn.x", (R, S.L_s, S.code_dim), torch.float32)
         N = S.L_s * S.code_dim
-        self.launches += 1
-        L.check(self.lib.stzs_state_init(x.data_ptr(), eps.data_ptr(), B, N, int(cfg), float(sig[0]), self.stream()),
-                "state_init")
+        self._raw(self.lib.stzs_state_init, "state_init", x.data_ptr(), eps.data_ptr(), B, N, int(cfg), float(sig[0]))
         D = self.act("dn.D", R, S.L_s, S.code_dim, torch.float32)
         for i in range(steps):
             self.denoiser_step(st, i, Act(x), D)
-            self.launches += 1
-            L.check(self.lib.stzs_cfg_euler(x.data_ptr(), D.t.data_ptr(), B, N, int(cfg), float(cfg_scale),
-                                            float(sig[i]), float(sig[i + 1] - sig[i]), self.stream()), "cfg_euler")
+            self._raw(self.lib.stzs_cfg_euler, "cfg_euler", x.data_ptr(), D.t.data_ptr(), B, N, int(cfg),
+                      float(cfg_scale), float(sig[i]), float(sig[i + 1] - sig[i]))
         return x[:B]
 
     def denoiser_fwd(self, h_txt: Act, prompt: torch.Tensor, x: torch.Tensor, sigma: float, cfg: bool) -> torch.Tensor:
@@ -947,20 +1019,14 @@ class StyleTTSZS:
             f32 = self.sdt == torch.float32
             nul = Act(W.t(W.dn_ctx_null32 if f32 else W.dn_ctx_null)[None])
             dst = Act(ctx.t[B:]).rows(0, B)
-            a = L.CopyArgs()
-            a.x, a.y = nul.ptr, dst.t.data_ptr() + T * ctx.ld * ctx.t.element_size()
-            a.ldx, a.bsx, a.ldy, a.bsy = d, 0, ctx.ld, Lc * ctx.ld
-            a.B, a.R, a.C, a.in_dtype, a.out_dtype = B, Ls, d, nul.dt, ctx.dt
-            self._call(self.lib.stzs_copy2d, a, "ctx_null")
+            self._copy_rows(nul.ptr, d, 0, dst.t.data_ptr() + T * ctx.ld * ctx.t.element_size(), ctx.ld, Lc * ctx.ld,
+                            B, Ls, d, nul.dt, ctx.dt, "ctx_null")
         pm = self.mean_rows(prompt, 0, cd, "dn.pm")
         pool = self.buf("dn.pool", (R, d), torch.float32)
         self.conv(W.dn_pool, Act(pm[:, None]), Act(pool[:B, None]), rows=self._rows_z(W.dn_pool), what="dn.pool")
         if cfg:
-            a = L.CopyArgs()
-            a.x, a.y = W.t(W.dn_pool_null).data_ptr(), pool[B:].data_ptr()
-            a.ldx, a.bsx, a.ldy, a.bsy = d, 0, d, d
-            a.B, a.R, a.C, a.in_dtype, a.out_dtype = B, 1, d, L.F32, L.F32
-            self._call(self.lib.stzs_copy2d, a, "pool_null")
+            self._copy_rows(W.t(W.dn_pool_null).data_ptr(), d, 0, pool[B:].data_ptr(), d, d, B, 1, d, L.F32, L.F32,
+                            "pool_null")
         kv = []
         if getattr(W, "dn_kv_all", None) is not None and self.kv_fuse:
             # (r06) all layers' K / V of the shared context in one linear (weights.py dn_kv_all); layer l's [K | V] are
@@ -989,16 +1055,14 @@ class StyleTTSZS:
         fmod = self.buf("dn.fmod", (steps * R, 2 * d), torch.float32)
         modx = self.buf("dn.modx", (S.dn_layers, steps * R, 6 * d), torch.float32)
         fmodx = self.buf("dn.fmodx", (1, steps * R, 2 * d), torch.float32)
-        self.launches += 1
         cond = self.lib.stzs_dn_cond_steps_f32 if cb.dtype == torch.float32 else self.lib.stzs_dn_cond_steps
-        L.check(cond(pool.data_ptr(), temb.t.data_ptr(), cb.data_ptr(), R, d, steps, self.stream()), "dn_cond_steps")
+        self._raw(cond, "dn_cond_steps", pool.data_ptr(), temb.t.data_ptr(), cb.data_ptr(), R, d, steps)
         self.conv(W.dn_ada, Act(cb[:, None]), Act(mod[:, None]), what="dn.ada")
         self.conv(W.dn_final_ada, Act(cb[:, None]), Act(fmod[:, None]), what="dn.final_ada")
-        self.launches += 2
-        L.check(self.lib.stzs_adaln_expand(mod.data_ptr(), W.t(W.dn_table).data_ptr(), modx.data_ptr(), steps * R, d,
-                                           6, S.dn_layers, 0b010010, self.stream()), "adaln_expand")
-        L.check(self.lib.stzs_adaln_expand(fmod.data_ptr(), None, fmodx.data_ptr(), steps * R, d, 2, 1, 0b10,
-                                           self.stream()), "adaln_expand.f")
+        self._raw(self.lib.stzs_adaln_expand, "adaln_expand", mod.data_ptr(), W.t(W.dn_table).data_ptr(),
+                  modx.data_ptr(), steps * R, d, 6, S.dn_layers, 0b010010)
+        self._raw(self.lib.stzs_adaln_expand, "adaln_expand.f", fmod.data_ptr(), None, fmodx.data_ptr(), steps * R, d,
+                  2, 1, 0b10)
         return dict(R=R, sig=list(sigmas), kv=kv, modx=modx, fmodx=fmodx)
 
     def denoiser_step(self, st: dict, i: int, xa: Act, D: Act):
@@ -1247,9 +1311,7 @@ class StyleTTSZS:
         c0, c1, c2 = S.f0n_ch
 
         s0 = self.stats(xs, "pr.xs.s1")  # (both branches' first AdaIN normalise xs: its statistics once, r06)
-        bs = self.branch_streams
-        forked = bs is True or (isinstance(bs, (set, frozenset)) and "f0n" in bs)
-        if self.f0n_pair and self.blk_splitk and not forked:
+        if self.f0n_pair and self.blk_splitk and not self._fork_on("f0n"):
             # (r06) the two branches in lockstep, each block's two convs of both branches as one launch pair
             # (stzs_conv1d_group -> conv_mfma_pair / splitk_epi_pair): same bits as branch after branch
             ys = {br: (self.act(f"pr.{br}.y0", B, T40, c0, self.adt), self.act(f"pr.{br}.y1", B, T80, c1, self.adt),
@@ -1284,91 +1346,73 @@ class StyleTTSZS:
     def blk(self, bw, x: Act, out: Act, ng, gb: torch.Tensor, key, dt=torch.bfloat16, s1=None):
         """AdainResBlk1d: out = (conv2(act(AdaIN(conv1(up(act(AdaIN(x))))))) + sc(x)) / sqrt 2.
         s1: x's statistics when the caller already has them (self.stats(x, ...))."""
-        B, T = x.B, x.T
-        off1, n1 = ng.offsets[bw.name + ".norm1"]
-        off2, n2 = ng.offsets[bw.name + ".norm2"]
-        gbase, gbs = gb.data_ptr(), ng.total
-        m1, r1, sb1 = s1 if s1 is not None else self.stats(x, key + ".s1")
-        # batch-1 engine: the generic-layout copies split-K (blk_splitk), else the register-direct convs
-        sk = self.blk_splitk if dt == torch.bfloat16 else 0
-        c1 = bw.conv1s if (sk and bw.conv1s is not None) else bw.conv1
-        c2 = bw.conv2s if (sk and bw.conv2s is not None) else bw.conv2
-        To = 2 * T if bw.up else T
-        r = self.act(key + ".r", B, To, bw.dout, dt)
-        if bw.up:
-            u = self.act(key + ".u", B, To, bw.din, dt)
-            a = L.DwupArgs()
-            a.x, a.y, a.mean, a.rstd, a.gb = x.ptr, u.ptr, m1.data_ptr(), r1.data_ptr(), gbase + off1 * 4
-            a.w, a.wb = self.W.t(bw.pool_w).data_ptr(), self.W.t(bw.pool_b).data_ptr()
-            a.ldx, a.bsx, a.ldy, a.bsy, a.stat_bs, a.gb_bs, a.gb_beta_off = x.ld, x.bs, u.ld, u.bs, sb1, gbs, n1
-            a.B, a.T, a.C, a.slope, a.dtype = B, T, bw.din, 0.2, x.dt
-            self._call(self.lib.stzs_adain_dwup, a, key + ".dwup")
-            _, (m2, r2, sb2) = self.conv(c1, u, r, pad=1, stats_key=key + ".s2", splitk=sk, what=key + ".conv1")
-        else:
-            _, (m2, r2, sb2) = self.conv(c1, x, r, pad=1, pro=(m1, r1, sb1, gbase + off1 * 4, gbs, n1),
-                                         pro_act=L.ACT_LEAKY, pro_slope=0.2, stats_key=key + ".s2", splitk=sk,
-                                         what=key + ".conv1")
-        if bw.sc is not None:
-            scb = self.act(key + ".sc", B, T, bw.dout, dt)
-            self.conv(bw.scs if (sk and bw.scs is not None) else bw.sc, x, scb, splitk=sk, what=key + ".sc")
-            res = scb
-        else:
-            res = x
-        self.conv(c2, r, out, pad=1, pro=(m2, r2, sb2, gbase + off2 * 4, gbs, n2), pro_act=L.ACT_LEAKY,
-                  pro_slope=0.2, res=res, res_tdiv=2 if bw.up else 1, alpha=1.0 / math.sqrt(2.0), splitk=sk,
-                  what=key + ".conv2")
+        s1 = s1 if s1 is not None else self.stats(x, key + ".s1")
+        r, s2 = self._blk_conv1(bw, x, s1, ng, gb, key, dt)
+        self._blk_conv2(bw, r, s2, self._blk_shortcut(bw, x, key, dt), out, ng, gb, key, dt)
         return out
 
     def _blk_pair(self, items, ng, gb: torch.Tensor, dt):
         """blk() for two independent blocks of the same shape (items: (bw, x, out, key, s1) each), advanced side by
         side: statistics, upsampling and shortcuts one block after the other, each conv pair collected into one
         stzs_conv1d_group call (the library pairs the batch-1 DEEP split-K convs, else runs them in turn)."""
-        gbase, gbs = gb.data_ptr(), ng.total
-        sk = self.blk_splitk if dt == torch.bfloat16 else 0
-        st = []
-        for bw, x, out, key, s1 in items:
-            m1, r1, sb1 = s1 if s1 is not None else self.stats(x, key + ".s1")
-            st.append((m1, r1, sb1))
+        st = [s1 if s1 is not None else self.stats(x, key + ".s1") for _, x, _, key, s1 in items]
         refs = [m.ref for m, _, _ in st if isinstance(m, _StatPtr) and not m.ref.done]
         if len(refs) == len(items) and len({id(r) for r in refs}) == len(refs) and all(it[0].up for it in items):
             self._finalize_group(refs)  # (the upsampling blocks' dwup reads mean / rstd: both finalised in one launch)
-        grp, st2, rs = [], [], []
-        for (bw, x, out, key, _), (m1, r1, sb1) in zip(items, st):
-            off1, n1 = ng.offsets[bw.name + ".norm1"]
-            c1 = bw.conv1s if (sk and bw.conv1s is not None) else bw.conv1
-            To = 2 * x.T if bw.up else x.T
-            r = self.act(key + ".r", x.B, To, bw.dout, dt)
-            rs.append(r)
-            if bw.up:
-                u = self.act(key + ".u", x.B, To, bw.din, dt)
-                a = L.DwupArgs()
-                a.x, a.y, a.mean, a.rstd, a.gb = x.ptr, u.ptr, m1.data_ptr(), r1.data_ptr(), gbase + off1 * 4
-                a.w, a.wb = self.W.t(bw.pool_w).data_ptr(), self.W.t(bw.pool_b).data_ptr()
-                a.ldx, a.bsx, a.ldy, a.bsy, a.stat_bs, a.gb_bs, a.gb_beta_off = x.ld, x.bs, u.ld, u.bs, sb1, gbs, n1
-                a.B, a.T, a.C, a.slope, a.dtype = x.B, x.T, bw.din, 0.2, x.dt
-                self._call(self.lib.stzs_adain_dwup, a, key + ".dwup")
-                _, s2 = self.conv(c1, u, r, pad=1, stats_key=key + ".s2", splitk=sk, collect=grp, what=key + ".conv1")
-            else:
-                _, s2 = self.conv(c1, x, r, pad=1, pro=(m1, r1, sb1, gbase + off1 * 4, gbs, n1), pro_act=L.ACT_LEAKY,
-                                  pro_slope=0.2, stats_key=key + ".s2", splitk=sk, collect=grp, what=key + ".conv1")
-            st2.append(s2)
-        self._launch_group(grp, "blk.conv1")
-        res = []
-        for bw, x, out, key, _ in items:
-            if bw.sc is not None:
-                scb = self.act(key + ".sc", x.B, x.T, bw.dout, dt)
-                self.conv(bw.scs if (sk and bw.scs is not None) else bw.sc, x, scb, splitk=sk, what=key + ".sc")
-                res.append(scb)
-            else:
-                res.append(x)
         grp = []
-        for (bw, x, out, key, _), (m2, r2, sb2), r, rr in zip(items, st2, rs, res):
-            off2, n2 = ng.offsets[bw.name + ".norm2"]
-            c2 = bw.conv2s if (sk and bw.conv2s is not None) else bw.conv2
-            self.conv(c2, r, out, pad=1, pro=(m2, r2, sb2, gbase + off2 * 4, gbs, n2), pro_act=L.ACT_LEAKY,
-                      pro_slope=0.2, res=rr, res_tdiv=2 if bw.up else 1, alpha=1.0 / math.sqrt(2.0), splitk=sk,
-                      collect=grp, what=key + ".conv2")
+        rs = [self._blk_conv1(bw, x, s1, ng, gb, key, dt, collect=grp) for (bw, x, _, key, _), s1 in zip(items, st)]
+        self._launch_group(grp, "blk.conv1")
+        res = [self._blk_shortcut(bw, x, key, dt) for bw, x, _, key, _ in items]
+        grp = []
+        for (bw, _, out, key, _), (r, s2), rr in zip(items, rs, res):
+            self._blk_conv2(bw, r, s2, rr, out, ng, gb, key, dt, collect=grp)
         self._launch_group(grp, "blk.conv2")
+
+    def _blk_weights(self, bw, dt):
+        """-> (conv1, conv2, shortcut | None, split-K slices) of an AdaIN block: in the batch-1 engine the
+        generic-layout copies split-K (blk_splitk), else the register-direct convs"""
+        sk = self.blk_splitk if dt == torch.bfloat16 else 0
+        pick = lambda s, c: s if (sk and s is not None) else c
+        return pick(bw.conv1s, bw.conv1), pick(bw.conv2s, bw.conv2), \
+            (None if bw.sc is None else pick(bw.scs, bw.sc)), sk
+
+    def _blk_conv1(self, bw, x: Act, s1, ng, gb: torch.Tensor, key, dt, collect=None):
+        """a block's conv1 over act(AdaIN(x)) -- in an upsampling block over the x2 depthwise ConvTranspose of it
+        (stzs_adain_dwup) -- with its output's statistics fused -> (r, (mean, rstd, stat_bs) of r)"""
+        c1, _, _, sk = self._blk_weights(bw, dt)
+        m1, r1, sb1 = s1
+        off1, n1 = ng.offsets[bw.name + ".norm1"]
+        gb1, gbs = gb.data_ptr() + off1 * 4, ng.total
+        To = 2 * x.T if bw.up else x.T
+        r = self.act(key + ".r", x.B, To, bw.dout, dt)
+        kw = dict(pad=1, stats_key=key + ".s2", splitk=sk, collect=collect, what=key + ".conv1")
+        if not bw.up:
+            return r, self.conv(c1, x, r, pro=(m1, r1, sb1, gb1, gbs, n1), pro_act=L.ACT_LEAKY, pro_slope=0.2, **kw)[1]
+        u = self.act(key + ".u", x.B, To, bw.din, dt)
+        a = L.DwupArgs()
+        a.x, a.y, a.mean, a.rstd, a.gb = x.ptr, u.ptr, m1.data_ptr(), r1.data_ptr(), gb1
+        a.w, a.wb = self.W.t(bw.pool_w).data_ptr(), self.W.t(bw.pool_b).data_ptr()
+        a.ldx, a.bsx, a.ldy, a.bsy, a.stat_bs, a.gb_bs, a.gb_beta_off = x.ld, x.bs, u.ld, u.bs, sb1, gbs, n1
+        a.B, a.T, a.C, a.slope, a.dtype = x.B, x.T, bw.din, 0.2, x.dt
+        self._call(self.lib.stzs_adain_dwup, a, key + ".dwup")
+        return r, self.conv(c1, u, r, **kw)[1]
+
+    def _blk_shortcut(self, bw, x: Act, key, dt) -> Act:
+        """a block's residual input: its 1x1 shortcut conv of x, or x itself"""
+        _, _, sc, sk = self._blk_weights(bw, dt)
+        if sc is None:
+            return x
+        scb = self.act(key + ".sc", x.B, x.T, bw.dout, dt)
+        return self.conv(sc, x, scb, splitk=sk, what=key + ".sc")
+
+    def _blk_conv2(self, bw, r: Act, s2, res: Act, out: Act, ng, gb: torch.Tensor, key, dt, collect=None):
+        """a block's conv2 over act(AdaIN(r)), plus the residual, / sqrt 2 -> out"""
+        _, c2, _, sk = self._blk_weights(bw, dt)
+        m2, r2, sb2 = s2
+        off2, n2 = ng.offsets[bw.name + ".norm2"]
+        self.conv(c2, r, out, pad=1, pro=(m2, r2, sb2, gb.data_ptr() + off2 * 4, ng.total, n2), pro_act=L.ACT_LEAKY,
+                  pro_slope=0.2, res=res, res_tdiv=2 if bw.up else 1, alpha=1.0 / math.sqrt(2.0), splitk=sk,
+                  collect=collect, what=key + ".conv2")
 
     # ------------------------------------------------------------------ (c) decoder
     def decode(self, pro: dict, codes: torch.Tensor, seeds, istft=True) -> torch.Tensor:
@@ -1578,13 +1622,6 @@ class StyleTTSZS:
             out.append((a, min(a + chunk, T40), wa, wa + W))
         return out
 
-    def _copy_rows(self, x: int, ldx: int, bsx: int, y: int, ldy: int, bsy: int, nb: int, R: int, Cn: int, dti, dto):
-        """stzs_copy2d on raw byte addresses: nb blocks of R rows x Cn columns (source block stride bsx elements)"""
-        a = L.CopyArgs()
-        a.x, a.y, a.ldx, a.bsx, a.ldy, a.bsy = x, y, ldx, bsx, ldy, bsy
-        a.B, a.R, a.C, a.in_dtype, a.out_dtype = nb, R, Cn, dti, dto
-        self._call(self.lib.stzs_copy2d, a, "copy_windows")
-
     def decode_chunked(self, pro: dict, codes: torch.Tensor, seeds, chunk: int, halo: int, batch_windows=True,
                        max_pass_rows: int = 64):
         """configs[4] CHUNKED streaming decoder (oracle/stzs_ref.py decode_chunked): each chunk of `chunk` aligned
@@ -1677,25 +1714,14 @@ class StyleTTSZS:
         wav = self.buf("gen.wav_stream", (B, Nout), torch.float32)
         ncol = _rup(S.n_fft + 2, 4)
         tails = [self.buf("gen.tail0", (B, 8, ncol), torch.float32), self.buf("gen.tail1", (B, 8, ncol), torch.float32)]
-        n0, n1 = C.c_int64(), C.c_int64()
         f0, i = 0, 0
         while f0 < Tf:
             Fc = min(chunk_frames, Tf - f0)
             if 0 < Tf - f0 - Fc < 2:  # fold a 1-frame remainder (Tf = 600*T40/5 + 1) into this chunk
                 Fc = Tf - f0
-            fin = int(f0 + Fc == Tf)
-            halo = self.lib.stzs_istft_stream_span(f0, Fc, fin, S.n_fft, S.istft_hop, C.byref(n0), C.byref(n1))
-            L.check(min(halo, 0), "istft_stream_span")
-            assert halo <= 8
-            a = L.IstftStreamArgs()
-            a.post = post.ptr + f0 * post.ld * 4
-            a.tail_in = tails[i % 2].data_ptr() if f0 > 0 else None
-            a.tail_out = tails[(i + 1) % 2].data_ptr() if not fin else None
-            a.wav = wav.data_ptr() + n0.value * 4
-            a.ldp, a.bsp, a.bsw, a.ldt = post.ld, post.bs, Nout, ncol
-            a.B, a.f0, a.Fc, a.final_chunk, a.n_fft, a.hop_s = B, f0, Fc, fin, S.n_fft, S.istft_hop
-            self._call(self.lib.stzs_istft_stream, a, "istft_stream")
-            yield n0.value, wav[:, n0.value:n1.value]
+            n0, n1 = self._istft_chunk(post.ptr + f0 * post.ld * 4, post.ld, post.bs, B, f0, Fc, int(f0 + Fc == Tf),
+                                       wav, tails, i)
+            yield n0, wav[:, n0:n1]
             f0 += Fc
             i += 1
 
@@ -1711,14 +1737,27 @@ class StyleTTSZS:
         """the statistics of up to three collected convs finalised in one launch (stzs_chan_stats_final_group)"""
         arr = (L.StatsArgs * len(refs))()
         for s, r in zip(arr, refs):
-            s.mean, s.rstd, s.partial = r.mean.data_ptr(), r.rstd.data_ptr(), r.part.data_ptr()
-            s.stat_bs, s.B, s.T, s.C, s.eps = r.ld, r.B, r.T, r.ld, 1e-5
+            r.final_args(s)
         assert len({r.chunk_rows for r in refs}) == 1
-        self.launches += 1
-        L.check(self.lib.stzs_chan_stats_final_group(arr, len(refs), refs[0].chunk_rows, self.stream()),
-                "chan_stats_final_group")
+        self._raw(self.lib.stzs_chan_stats_final_group, "chan_stats_final_group", arr, len(refs), refs[0].chunk_rows)
         for r in refs:
             r.done = True
+
+    def _rb_c1(self, lw, x: Act, y: Act, st, gbd, ng, stats_key, collect=None):
+        """a resblock layer's first conv (dilated) over Snake(AdaIN(x)), st = x's (mean, rstd, stat_bs), with y's
+        statistics fused -> (mean, rstd, stat_bs) of y"""
+        k, dil = lw["k"], lw["dil"]
+        o1, c1 = ng.offsets[lw["n1"]]
+        return self.conv(lw["c1"], x, y, pad=dil * (k - 1) // 2, dil=dil,
+                         pro=(*st, gbd.data_ptr() + o1 * 4, ng.total, c1), pro_act=L.ACT_SNAKE, pro_alpha=lw["a1"],
+                         stats_key=stats_key, collect=collect, what="rb.c1")[1]
+
+    def _rb_c2(self, lw, x: Act, y: Act, st, res: Act, gbd, ng, **kw):
+        """a resblock layer's second conv over Snake(AdaIN(x)) + res; kw: the caller's epilogue / statistics /
+        collect arguments -> conv()'s result"""
+        o2, c2 = ng.offsets[lw["n2"]]
+        return self.conv(lw["c2"], x, y, pad=(lw["k"] - 1) // 2, pro=(*st, gbd.data_ptr() + o2 * 4, ng.total, c2),
+                         pro_act=L.ACT_SNAKE, pro_alpha=lw["a2"], res=res, what="rb.c2", **kw)
 
     def _mrf_trio(self, x: Act, i, gbd, ng):
         """mrf() with the three resblocks (k 3 / 7 / 11) advanced layer by layer side by side: each layer's c1 convs in
@@ -1727,7 +1766,6 @@ class StyleTTSZS:
         resblocks' sum, acc_in).  Per-resblock buffers; every value bit-identical to mrf()'s order."""
         S, W = self.spec, self.W
         B, T, c = x.B, x.T, x.C
-        gbase, gbs = gbd.data_ptr(), ng.total
         dt = x.t.dtype
         nk = len(S.rb_kernels)
         xs = self.act(f"gen.xs{i}", B, T, c, dt)
@@ -1737,48 +1775,38 @@ class StyleTTSZS:
         cur, cm, cr = [x] * nk, [mx] * nk, [rx] * nk
         nl = len(W.rb[i][0])
         for m in range(nl):
-            grp, st1 = [], []
-            for j, res in enumerate(W.rb[i]):
-                lw = res[m]
-                k, dil = lw["k"], lw["dil"]
-                o1, c1 = ng.offsets[lw["n1"]]
-                _, st = self.conv(lw["c1"], cur[j], t1[j], pad=dil * (k - 1) // 2, dil=dil,
-                                  pro=(cm[j], cr[j], sb, gbase + o1 * 4, gbs, c1), pro_act=L.ACT_SNAKE,
-                                  pro_alpha=lw["a1"], stats_key=f"gen.st{i}.{j}", collect=grp, what="rb.c1")
-                st1.append(st)
+            grp = []
+            st1 = [self._rb_c1(res[m], cur[j], t1[j], (cm[j], cr[j], sb), gbd, ng, f"gen.st{i}.{j}", collect=grp)
+                   for j, res in enumerate(W.rb[i])]
             self._launch_group(grp, "rb.c1")
             self._finalize_group([st[0].ref for st in st1])
-            last = m == nl - 1
-            grp, st2, outs = [], [], []
-            for j, res in enumerate(W.rb[i]):
-                lw = res[m]
-                k = lw["k"]
-                o2, c2 = ng.offsets[lw["n2"]]
-                tm, tr, _ = st1[j]
-                kw = dict(pad=(k - 1) // 2, pro=(tm, tr, sb, gbase + o2 * 4, gbs, c2), pro_act=L.ACT_SNAKE,
-                          pro_alpha=lw["a2"], res=cur[j], what="rb.c2")
-                if last:  # xs = c2 / nk + cur (+ xs): the resblocks' sum in resblock order, one launch each
-                    self.conv(lw["c2"], t1[j], xs, alpha=1.0 / nk, acc_in=(xs if j > 0 else None), beta=1.0, **kw)
-                else:
-                    out = bufs[j][0] if cur[j] is not bufs[j][0] else bufs[j][1]
-                    _, st = self.conv(lw["c2"], t1[j], out, stats_key=f"gen.sc{i}.{j}.{m % 2}", collect=grp, **kw)
-                    st2.append(st)
-                    outs.append(out)
-            if not last:
-                self._launch_group(grp, "rb.c2")
-                self._finalize_group([st[0].ref for st in st2])
-                for j in range(nk):
-                    cur[j], (cm[j], cr[j], _) = outs[j], st2[j]
+            if m == nl - 1:  # xs = c2 / nk + cur (+ xs): the resblocks' sum in resblock order, one launch each
+                for j, res in enumerate(W.rb[i]):
+                    self._rb_c2(res[m], t1[j], xs, (*st1[j][:2], sb), cur[j], gbd, ng, alpha=1.0 / nk,
+                                acc_in=(xs if j > 0 else None), beta=1.0)
+                break
+            grp = []
+            outs = [bufs[j][0] if cur[j] is not bufs[j][0] else bufs[j][1] for j in range(nk)]
+            st2 = [self._rb_c2(res[m], t1[j], outs[j], (*st1[j][:2], sb), cur[j], gbd, ng,
+                               stats_key=f"gen.sc{i}.{j}.{m % 2}", collect=grp)[1] for j, res in enumerate(W.rb[i])]
+            self._launch_group(grp, "rb.c2")
+            self._finalize_group([st[0].ref for st in st2])
+            for j in range(nk):
+                cur[j], (cm[j], cr[j], _) = outs[j], st2[j]
         return xs
+
+    def _mrf_trio_on(self, x: Act, i) -> bool:
+        """the side-by-side schedule applies: small batch, no timer running (its collected convs are not timed), and
+        the stage's resblocks are the k 3 / 7 / 11 trio of equal depth the library groups"""
+        rb = self.W.rb[i]
+        return (self.mrf_trio and self.timer is None and x.B <= 4 and tuple(self.spec.rb_kernels) == (3, 7, 11) and
+                len({len(res) for res in rb}) == 1 and all(r["k"] == k for res, k in zip(rb, (3, 7, 11)) for r in res))
 
     def mrf(self, x: Act, i, gbd, ng):
         S, W = self.spec, self.W
-        if (self.mrf_trio and self.timer is None and x.B <= 4 and tuple(S.rb_kernels) == (3, 7, 11) and
-                len({len(res) for res in W.rb[i]}) == 1 and all(r["k"] == k for res, k in zip(W.rb[i], (3, 7, 11))
-                                                               for r in res)):
+        if self._mrf_trio_on(x, i):
             return self._mrf_trio(x, i, gbd, ng)
         B, T, c = x.B, x.T, x.C
-        gbase, gbs = gbd.data_ptr(), ng.total
         dt = x.t.dtype
         xs = self.act(f"gen.xs{i}", B, T, c, dt)
         bufA = self.act(f"gen.ba{i}", B, T, c, dt)
@@ -1789,18 +1817,12 @@ class StyleTTSZS:
         for j, res in enumerate(W.rb[i]):
             cur, cm, cr = x, mx, rx
             for m, lw in enumerate(res):
-                k, dil = lw["k"], lw["dil"]
-                o1, c1 = ng.offsets[lw["n1"]]
-                o2, c2 = ng.offsets[lw["n2"]]
-                _, (tm, tr, _) = self.conv(lw["c1"], cur, t1, pad=dil * (k - 1) // 2, dil=dil,
-                                           pro=(cm, cr, sb, gbase + o1 * 4, gbs, c1), pro_act=L.ACT_SNAKE,
-                                           pro_alpha=lw["a1"], stats_key=f"gen.st{i}", what="rb.c1")
+                tm, tr, _ = self._rb_c1(lw, cur, t1, (cm, cr, sb), gbd, ng, f"gen.st{i}")
                 last = m == len(res) - 1
                 out = xs if last else (bufA if cur is not bufA else bufB)
-                r2 = self.conv(lw["c2"], t1, out, pad=(k - 1) // 2, pro=(tm, tr, sb, gbase + o2 * 4, gbs, c2),
-                               pro_act=L.ACT_SNAKE, pro_alpha=lw["a2"], res=cur, alpha=(1.0 / nk) if last else 1.0,
-                               acc_in=(xs if (last and j > 0) else None), beta=1.0,
-                               stats_key=None if last else f"gen.sc{i}.{m % 2}", what="rb.c2")
+                r2 = self._rb_c2(lw, t1, out, (tm, tr, sb), cur, gbd, ng, alpha=(1.0 / nk) if last else 1.0,
+                                 acc_in=(xs if (last and j > 0) else None), beta=1.0,
+                                 stats_key=None if last else f"gen.sc{i}.{m % 2}")
                 if not last:
                     _, (cm, cr, _) = r2
                     cur = out
@@ -1855,40 +1877,17 @@ class StyleTTSZS:
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
         -> dict(wav=[B, 600*T40], prompt_idx=[B|1, L_s, G], status=int32 [1], ...)"""
-        out = self._synth(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx)
+        h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
+                                                   n_frames, prompt_idx)
+        wav = self.decode(pro, codes, seeds)
         if check and not self._capturing():
             self.check_status()
-        return out
+        return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
 
-    def _synth(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx):
-        S = self.spec
-        dev = self.device
-        tokens = tokens.to(dev, torch.int32) if tokens.device != dev or tokens.dtype != torch.int32 else tokens
-        B = tokens.shape[0]
-        h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx)
-        pidx = self.prompt_idx
-        if prompt.shape[0] == 1 and B > 1:
-            pe = self.buf("prompt.bc", (B, S.L_s, S.code_dim), torch.float32)
-            pe.copy_(prompt.expand(B, -1, -1))
-            prompt = pe
-        if codes is None:
-            eps = noise.to(dev, torch.float32)
-            codes = self.sample_style(h, prompt, eps, steps, cfg_scale)
-        pro = self.predict_prosody(h, codes, durations, n_frames)
-        seeds = list(range(B)) if seeds is None else seeds
-        wav = self.decode(pro, codes, seeds)
-        return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=pidx, status=self.status, **pro)
-
-
-    def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
-                     codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None):
-        """configs[4] long-form synthesis with the streaming iSTFT decoder (SURVEY §8(a) a14): the text,
-        style, prosody and conv stack run over the whole target (AdaIN instance statistics are
-        utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
-        (first_sample, wav_chunk [B, n]) device views; their concatenation equals synth()["wav"].
-        chunked_halo=H: the CHUNKED decoder instead (decode_chunked: every `chunk_s` chunk decoded over a window of
-        +-H aligned frames with window-local statistics -- a different function, parity vs oracle decode_chunked):
-        the first chunk is ready after the front and one window's decode."""
+    def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx):
+        """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
+        encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
+        -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
         S = self.spec
         dev = self.device
         tokens = tokens.to(dev, torch.int32) if tokens.device != dev or tokens.dtype != torch.int32 else tokens
@@ -1901,7 +1900,20 @@ class StyleTTSZS:
         if codes is None:
             codes = self.sample_style(h, prompt, noise.to(dev, torch.float32), steps, cfg_scale)
         pro = self.predict_prosody(h, codes, durations, n_frames)
-        seeds = list(range(B)) if seeds is None else seeds
+        return h, prompt, codes, pro, list(range(B)) if seeds is None else seeds
+
+    def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
+                     codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None):
+        """configs[4] long-form synthesis with the streaming iSTFT decoder (SURVEY §8(a) a14): the text,
+        style, prosody and conv stack run over the whole target (AdaIN instance statistics are
+        utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
+        (first_sample, wav_chunk [B, n]) device views; their concatenation equals synth()["wav"].
+        chunked_halo=H: the CHUNKED decoder instead (decode_chunked: every `chunk_s` chunk decoded over a window of
+        +-H aligned frames with window-local statistics -- a different function, parity vs oracle decode_chunked):
+        the first chunk is ready after the front and one window's decode."""
+        S = self.spec
+        _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
+                                              n_frames, prompt_idx)
         if chunked_halo is not None:  # the chunked decoder: chunk-local statistics, first audio after one window
             yield from self.decode_chunked(pro, codes, seeds, max(1, int(round(chunk_s * S.sr / S.frame40))),
                                            int(chunked_halo))
