@@ -462,7 +462,8 @@ int stzs_istft_stream_span(int f0, int Fc, int final_chunk, int n_fft, int hop_s
 /* ---- reference-prompt front end (csrc/frontend.hip) -------------------------
  * log-mel of the 3-s reference = stzs_stft_frames -> stzs_conv1d (bf16 DFT GEMM against the cos | -sin
  * basis, fp32 out) -> stzs_log_mel; the prompt encoder's k5 convs run on stzs_conv1d, its adaptive
- * average pooling on stzs_pool_rows. */
+ * average pooling on stzs_pool_rows.  The precise front end (fp32 throughout) takes stzs_stft_logmel for the three
+ * log-mel launches and the split-operand form of stzs_conv1d (STZS_CONV_W_X3 / _FRAG32X3) on fp32 rows. */
 /* y[b, t, m] = bf16(window[m] * x[reflect(t * hop + (n_fft - win) / 2 + m - n_fft / 2)]) for m < win,
  * 0 for win <= m < ldy: the windowed STFT frames of torch.stft(center=True, pad_mode="reflect") */
 typedef struct stzs_frames_args {
@@ -491,6 +492,29 @@ typedef struct stzs_pool_args {
     int32_t B, T, L, C, in_dtype, out_dtype;
 } stzs_pool_args;
 int stzs_pool_rows(const stzs_pool_args* a, void* stream);
+/* the PRECISE log-mel in one launch (csrc/stftmel.hip; StyleTTSZS(precise_frontend=True)): per (utterance b, frame t)
+ * one workgroup builds the frame of stzs_stft_frames in fp32 in LDS -- window[m] * x[reflect(t * hop + (n_fft - win) / 2
+ * + m - n_fft / 2)] for m < win, centred in n_fft, zeros around it -- runs an n_fft-point real FFT on it in fp32 (an
+ * n_fft / 2 point complex Stockham radix-4 / radix-2 transform of the even | odd packing and a split step, in LDS) and
+ * applies stzs_log_mel's sums to re^2 + im^2:
+ *   y[b, t, m] = log(max(sum_{k0 <= k < k1} fb[m][k] |X_t[k]|^2, 1e-5)), [k0, k1) = ranges[m], nbin = n_fft / 2 + 1.
+ * twiddle = the table [n_fft][2] of (cos, -sin)(2 pi q / n_fft) computed in float64 and rounded to fp32 on the host
+ * (stzs/weights.py stft_twiddles): the only source of trigonometric values, no device sincos.  A frame's result depends
+ * on its own samples only (no cross-workgroup reduction, no atomics): bit-identical for any B.  n_fft a power of two in
+ * 64..4096, win <= n_fft, N > n_fft / 2 (reflect padding, as torch), (F - 1) * hop <= N + n_fft, ldy >= n_mels,
+ * ldw >= N, B <= 65535.  Replaces stzs_stft_frames + the bf16 DFT GEMM + stzs_log_mel where the log-mel has to match
+ * the fp32 oracle (1.2e-3 L1 on the bf16 DFT, fp32 rounding here: DESIGN.md §3). */
+typedef struct stzs_stftmel_args {
+    const float* wav;      /* [B, ldw] f32, N samples each */
+    const float* window;   /* [win] f32 (periodic Hann) */
+    const float* twiddle;  /* [n_fft][2] f32: cos | -sin of 2 pi q / n_fft */
+    const float* fb;       /* [n_mels][n_fft / 2 + 1] f32 mel filterbank */
+    const int32_t* ranges; /* [n_mels][2] nonzero bin range of each filter */
+    void* y;               /* [B, F, ldy] bf16 | f32 */
+    int64_t ldw, ldy, bsy;
+    int32_t B, N, F, n_fft, win, hop, n_mels, out_dtype;
+} stzs_stftmel_args;
+int stzs_stft_logmel(const stzs_stftmel_args* a, void* stream);
 
 /* ---- discrete style codes (README.md:5 "fixed-length time-varying discrete style codes") ----
  * product vector quantiser over rows of C = G * dg fp32 values: group g of row r takes the codebook entry

@@ -147,6 +147,12 @@ class LogMelArgs(C.Structure):
                [(n, i32) for n in ("B", "F", "nbin", "n_mels", "out_dtype", "pad_i")]
 
 
+class StftMelArgs(C.Structure):
+    _fields_ = [(n, vp) for n in ("wav", "window", "twiddle", "fb", "ranges", "y")] + \
+               [(n, i64) for n in ("ldw", "ldy", "bsy")] + \
+               [(n, i32) for n in ("B", "N", "F", "n_fft", "win", "hop", "n_mels", "out_dtype")]
+
+
 class PoolArgs(C.Structure):
     _fields_ = [("x", vp), ("y", vp)] + [(n, i64) for n in ("ldx", "bsx", "ldy", "bsy")] + \
                [(n, i32) for n in ("B", "T", "L", "C", "in_dtype", "out_dtype")]
@@ -212,7 +218,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_lstm_state_reset", "stzs_predictor_prep",
            "stzs_durations", "stzs_alignment", "stzs_gather_rows", "stzs_adain_dwup", "stzs_f0n_down",
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
-           "stzs_stft_frames", "stzs_log_mel", "stzs_pool_rows", "stzs_code_quantize",
+           "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_code_quantize",
            "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler",
            "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_embed", "stzs_embed_f32", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
@@ -267,6 +273,7 @@ def load():
         "stzs_istft_stream_span": ([i32, i32, i32, i32, i32, P(i64), P(i64)], i32),
         "stzs_stft_frames": ([P(FramesArgs), vp], i32),
         "stzs_log_mel": ([P(LogMelArgs), vp], i32),
+        "stzs_stft_logmel": ([P(StftMelArgs), vp], i32),
         "stzs_pool_rows": ([P(PoolArgs), vp], i32),
         "stzs_code_quantize": ([P(VqArgs), vp], i32),
         "stzs_dn_cond_steps": ([vp, vp, vp, i32, i32, i32, vp], i32),

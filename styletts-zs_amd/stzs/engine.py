@@ -285,7 +285,7 @@ class _StatPtr:
 class StyleTTSZS:
     def __init__(self, spec: Spec, params, device="cuda:0", fill=True, fp8_denoiser=False, precise_decoder=False,
                  packed: PackedModel = None, branch_streams=False, precise=False, dn_splitk=None, dn_rows=None,
-                 te_splitk=None, blk_splitk=None, dur_overlap=None):
+                 te_splitk=None, blk_splitk=None, dur_overlap=None, precise_frontend=False):
         """packed: an already packed (e.g. RCCL-broadcast, stzs/dist.py) PackedModel on `device`; params unused.
         fp8_denoiser: run the per-layer denoiser linears (qkv, o, q, co, ff1, ff2) on e4m3fn MFMA with
         per-row activation / per-column weight scales (configs[4]); bf16 otherwise.
@@ -295,7 +295,12 @@ class StyleTTSZS:
         activations, split-operand convs / linears / LSTM recurrences, fp32 attention, libm activations) -- the
         mode that meets the north-star log-mel L1 <= 1e-3 END TO END vs the fp32 oracle (tools/precision_probe.py:
         2.2e-4 in emulation); bf16 weights/activations alone cost ~5e-2.  The reference-prompt
-        front end stays bf16: its output is quantised to discrete codes.
+        front end stays bf16: its output is quantised to discrete codes (precise_frontend=True makes it precise too).
+        precise_frontend: the reference-prompt front end in fp32, with any of the modes above -- the log-mel in one
+        launch (stzs_stft_logmel, csrc/stftmel.hip: fp32 FFT in LDS instead of the bf16 DFT GEMM), the prompt encoder's
+        convs, pooling and projection on fp32 activations and split bf16 operands.  The pre-quantiser features then
+        match the fp32 oracle to ~1e-5 (the bf16 front end flips ~0.6 % of the discrete codes), so synth() can be
+        compared with the oracle from the same reference wav with no code teacher-forced.
         branch_streams: run the independent branches (text encoder || prompt encoder, F0 || N predictor branches)
         on forked side streams (graph-capturable: the fork/join is stream-ordered); each branch has its own
         scratch (statistics slab / workspace), results bit-identical to the single-stream order.
@@ -311,6 +316,7 @@ class StyleTTSZS:
         # activations), text encoder / prosody predictor / decoder precise (the F0 phase the harmonic source
         # integrates over 30 s needs the predictor's fp32-level F0: DESIGN.md §3)
         self.lowp_dn = bool(precise and fp8_denoiser)
+        self.precise_frontend = bool(precise_frontend)
         self.dec_dt = torch.float32 if precise_decoder else torch.bfloat16
         self.adt = torch.float32 if precise else torch.bfloat16  # text / predictor activations
         self.sdt = torch.bfloat16 if self.lowp_dn else self.adt  # style-sampler activations
@@ -320,12 +326,13 @@ class StyleTTSZS:
         if packed is not None:
             assert packed.spec == spec and packed.arena.buf.device == self.device and \
                 packed.precise == precise_decoder and packed.precise_all == precise and \
-                getattr(packed, "lowp_denoiser", False) == self.lowp_dn, \
+                getattr(packed, "lowp_denoiser", False) == self.lowp_dn and \
+                getattr(packed, "precise_frontend", False) == self.precise_frontend, \
                 "packed model: spec / device / precise mode differ"
             self.W = packed
         else:
             self.W = PackedModel(spec, params, self.device, fill=fill, precise=precise_decoder, precise_all=precise,
-                                 lowp_denoiser=self.lowp_dn)
+                                 lowp_denoiser=self.lowp_dn, precise_frontend=self.precise_frontend)
         self._bufs = {}
         self._retired = []
         self._consts = {}
@@ -884,13 +891,27 @@ class StyleTTSZS:
         h = self.act("te.h", B, T, S.d_txt, self.adt)
         return self.lstm(W.te_lstm, e, h, "te.lstm")
 
-    def log_mel(self, wav: torch.Tensor, dtype=torch.bfloat16) -> Act:
+    def log_mel(self, wav: torch.Tensor, dtype=None) -> Act:
         """reference wav fp32 [B, N] (device) -> log-mel [B, N/hop + 1, n_mels]:
         windowed reflect-padded frames -> bf16 DFT GEMM on MFMA (cos | -sin basis, fp32 out) -> power, sparse
-        mel filterbank, log (csrc/frontend.hip)."""
+        mel filterbank, log (csrc/frontend.hip); precise_frontend: one stzs_stft_logmel launch (csrc/stftmel.hip).
+        dtype of the rows: bf16 | fp32, default the front end's own (fp32 when precise_frontend)."""
         S, W = self.spec, self.W
         B, N = wav.shape
         Fr = N // S.hop + 1
+        if dtype is None:
+            dtype = torch.float32 if self.precise_frontend else torch.bfloat16
+        if self.precise_frontend:
+            # one launch, everything in fp32: the frame, an FFT in LDS, power, mel, log (csrc/stftmel.hip)
+            mel = self.act("fe.mel", B, Fr, S.n_mels, dtype)
+            a = L.StftMelArgs()
+            a.wav, a.window, a.twiddle = wav.data_ptr(), W.t(W.fe_win).data_ptr(), W.t(W.fe_tw).data_ptr()
+            a.fb, a.ranges, a.y = W.t(W.fe_fb).data_ptr(), W.t(W.fe_rng).data_ptr(), mel.ptr
+            a.ldw, a.ldy, a.bsy = N, mel.ld, mel.bs
+            a.B, a.N, a.F, a.n_fft, a.win, a.hop = B, N, Fr, S.mel_nfft, S.mel_win, S.hop
+            a.n_mels, a.out_dtype = S.n_mels, mel.dt
+            self._call(self.lib.stzs_stft_logmel, a, "stft_logmel")
+            return mel
         dft = W.fe_dft
         frames = self.act("fe.frames", B, Fr, dft.ci_pad)
         a = L.FramesArgs()
@@ -951,14 +972,16 @@ class StyleTTSZS:
         B = wav.shape[0]
         mel = self.log_mel(wav)
         Fr = mel.T
-        c0 = self.act("fe.c0", B, Fr, S.pe_ch)
-        c1 = self.act("fe.c1", B, Fr, S.pe_ch)
+        # (precise_frontend: fp32 rows; the convs then take the split-operand route on the weights' hi | lo streams)
+        fdt = torch.float32 if self.precise_frontend else torch.bfloat16
+        c0 = self.act("fe.c0", B, Fr, S.pe_ch, fdt)
+        c1 = self.act("fe.c1", B, Fr, S.pe_ch, fdt)
         self.conv(W.pe_conv0, mel, c0, pad=2, epi_act=L.ACT_LEAKY, epi_slope=0.2, what="pe.conv0")
         self.conv(W.pe_conv1, c0, c1, pad=2, epi_act=L.ACT_LEAKY, epi_slope=0.2, what="pe.conv1")
-        pooled = self.act("fe.pool", B, S.L_s, S.pe_ch)
+        pooled = self.act("fe.pool", B, S.L_s, S.pe_ch, fdt)
         a = L.PoolArgs()
         a.x, a.y, a.ldx, a.bsx, a.ldy, a.bsy = c1.ptr, pooled.ptr, c1.ld, c1.bs, pooled.ld, pooled.bs
-        a.B, a.T, a.L, a.C, a.in_dtype, a.out_dtype = B, Fr, S.L_s, S.pe_ch, L.BF16, L.BF16
+        a.B, a.T, a.L, a.C, a.in_dtype, a.out_dtype = B, Fr, S.L_s, S.pe_ch, c1.dt, pooled.dt
         self._call(self.lib.stzs_pool_rows, a, "pool_rows")
         out = self.buf("prompt.z", (B, S.L_s, S.code_dim), torch.float32)
         self.conv(W.pe_proj, pooled, Act(out), what="pe.proj")

@@ -350,6 +350,13 @@ def dft_basis(n_fft: int, win: int) -> torch.Tensor:
     return torch.cat([torch.cos(ang), -torch.sin(ang)], 0).float()
 
 
+def stft_twiddles(n_fft: int) -> torch.Tensor:
+    """[n_fft, 2] fp32: (cos, -sin)(2 pi q / n_fft), q < n_fft, computed in float64 and rounded once -- the only
+    trigonometric values of the precise log-mel's in-LDS FFT (csrc/stftmel.hip, stzs_stft_logmel)."""
+    ang = 2.0 * math.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft
+    return torch.stack([torch.cos(ang), -torch.sin(ang)], 1).float().contiguous()
+
+
 @dataclass
 class NormGroup:
     """all AdaIN fc layers of one stage, packed as one linear; offsets per norm name."""
@@ -465,12 +472,16 @@ def pack_blk(A: Arena, P, name, up=False, x3=False) -> BlkW:
 class PackedModel:
     """All hot-path weights of spec v0 in kernel layouts, resident in one device arena."""
 
-    def __init__(self, spec: Spec, P, device, fill=True, precise=False, precise_all=False, lowp_denoiser=False):
+    def __init__(self, spec: Spec, P, device, fill=True, precise=False, precise_all=False, lowp_denoiser=False,
+                 precise_frontend=False):
         """precise: also pack the split-operand (hi | lo) streams of every decoder conv (StyleTTSZS(
         precise_decoder=True)); precise_all: of every conv, linear and LSTM of the pipeline except the
         reference-prompt front end, whose output is quantised to discrete codes (StyleTTSZS(precise=True)).
         lowp_denoiser (with precise_all): the denoiser's linears without the split streams -- the configs[4]
-        long-form mode StyleTTSZS(precise=True, fp8_denoiser=True): fp8 sampler, precise text / prosody / decoder."""
+        long-form mode StyleTTSZS(precise=True, fp8_denoiser=True): fp8 sampler, precise text / prosody / decoder.
+        precise_frontend: the reference-prompt front end in fp32 (StyleTTSZS(precise_frontend=True)): the FFT twiddle
+        table of stzs_stft_logmel instead of the bf16 DFT basis, and the split streams of the prompt encoder's convs
+        and projection; independent of the other three."""
         S = self.spec = spec
         xd = precise or precise_all
         xa = precise_all
@@ -483,7 +494,10 @@ class PackedModel:
         self.te_ln = [(A.add(f"te.ln{i}.g", P[f"te.ln{i}.g"]), A.add(f"te.ln{i}.b", P[f"te.ln{i}.b"])) for i in range(S.te_layers)]
         self.te_lstm = pack_lstm(A, "te.lstm", P, x3=xa)
         # --- reference-prompt front end (csrc/frontend.hip): DFT basis, window, mel filterbank, encoder ---
-        self.fe_dft = pack_conv(A, "fe.dft", dft_basis(S.mel_nfft, S.mel_win))
+        xf = bool(precise_frontend)
+        # (the bf16 DFT basis, 9.8 MB at n_fft 2048, is not packed for the precise front end: its FFT needs 16 KB)
+        self.fe_dft = None if xf else pack_conv(A, "fe.dft", dft_basis(S.mel_nfft, S.mel_win))
+        self.fe_tw = A.add("fe.tw", stft_twiddles(S.mel_nfft)) if xf else None
         self.fe_win = A.add("fe.win", torch.hann_window(S.mel_win).float())
         fb = mel_filterbank(S.n_mels, S.mel_nfft, S.sr)
         nz = fb > 0
@@ -494,9 +508,9 @@ class PackedModel:
                 rng[m, 0], rng[m, 1] = int(idx[0]), int(idx[-1]) + 1
         self.fe_fb = A.add("fe.fb", fb.contiguous())
         self.fe_rng = A.add("fe.fbr", rng)
-        self.pe_conv0 = pack_conv(A, "pe.conv0", P["pe.conv0.w"], P["pe.conv0.b"])
-        self.pe_conv1 = pack_conv(A, "pe.conv1", P["pe.conv1.w"], P["pe.conv1.b"])
-        self.pe_proj = pack_conv(A, "pe.proj", P["pe.proj.w"], P["pe.proj.b"])
+        self.pe_conv0 = pack_conv(A, "pe.conv0", P["pe.conv0.w"], P["pe.conv0.b"], x3=xf)
+        self.pe_conv1 = pack_conv(A, "pe.conv1", P["pe.conv1.w"], P["pe.conv1.b"], x3=xf)
+        self.pe_proj = pack_conv(A, "pe.proj", P["pe.proj.w"], P["pe.proj.b"], x3=xf)
         self.pe_vq = A.add("pe.vq", P["pe.vq"].float())  # [G][K][dg] codebooks (stzs_code_quantize)
         # --- denoiser ---
         L = lambda n: pack_conv(A, n, P[n + ".w"], P[n + ".b"], x3=xa)
@@ -628,6 +642,7 @@ class PackedModel:
         self.precise = precise
         self.precise_all = precise_all
         self.lowp_denoiser = bool(lowp_denoiser and precise_all)
+        self.precise_frontend = xf
 
     def t(self, name):
         return self.arena[name]
