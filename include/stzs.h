@@ -252,6 +252,12 @@ typedef struct stzs_rowln_args {
     /* out_dtype = STZS_F8: y holds e4m3fn codes of y / y_scale[r], y_scale[r] the power-of-two row
      * scale of stzs_quant_rows */
     float* y_scale;
+    /* optional ragged mask (NULL = none): the R rows are blocks of T rows (b = r / T, t = r % T) and a row with
+     * t >= lens[b] (clamped into [1, T]) is stored as exact zeros after the activation -- the zero padding a
+     * following conv sees at the end of a sequence of lens[b] rows.  Honoured by stzs_row_layernorm (every in / out
+     * dtype; an e4m3fn pad row gets zero codes and scale 1), not by the fused form stzs_ln_linear (STZS_EINVAL). */
+    const int32_t* lens;
+    int32_t T, pad_t;
 } stzs_rowln_args;
 int stzs_row_layernorm(const stzs_rowln_args* a, void* stream);
 /* the LayerNorm that feeds a small-M linear, fused into it (csrc/lnrows.hip; the configs[1] batch-1 denoiser's
@@ -292,6 +298,10 @@ typedef struct stzs_attn_args {
     void* o;
     int64_t ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso;
     int32_t R, Lq, Lk, heads, dh, precise;
+    /* optional per-row key counts [R] (NULL = every row attends to all Lk keys): row r attends to its first
+     * clamp(lk_rows[r], 1, Lk) keys, the same bits as a launch of that row alone with that Lk; k / v rows at or
+     * beyond it are never loaded */
+    const int32_t* lk_rows;
 } stzs_attn_args;
 int stzs_attention(const stzs_attn_args* a, void* stream);
 
@@ -322,6 +332,13 @@ typedef struct stzs_lstm_args {
      * (stzs/weights.py pack_lstm(x3=True)), h is exchanged as hi | lo bf16, the gates use libm expf / tanhf
      * and y is fp32 [b, t, dir*H + j].  0 = bf16 h / bf16 y. */
     uint32_t precise;
+    /* optional per-utterance lengths [B] (NULL = every utterance runs all T steps): at a step whose position t
+     * (forward: the step, reverse: T - 1 - step) is >= lens[b] (clamped into [1, T]) utterance b's state is reset
+     * to c = 0, h = 0 after the cell update and y[b, t] is stored as zeros.  Rows t < lens[b] are then the bits of
+     * a launch of that utterance alone with T = lens[b] (the reverse recurrence starts from the zero state at its
+     * own last row); what gx holds at t >= lens[b] is ignored.  Steps, exchange and barriers are those of the
+     * uniform call. */
+    const int32_t* lens;
 } stzs_lstm_args;
 #define STZS_STATUS_LSTM_TIMEOUT 1u
 size_t stzs_lstm_workspace(int B, int H, int ndir);
@@ -342,17 +359,22 @@ int stzs_lstm_state_reset(void* sync, void* xchg, void* stream);
 
 /* ---- predictor glue ---- */
 /* per-token style: linear resample of codes[:, :, c0:c0+Cs] (L_s rows) to T rows (F.interpolate
- * linear, align_corners=False) into y[b, t, yc0 + c], plus copy of h[b, t, 0:Ch] to y[..., 0:Ch] */
+ * linear, align_corners=False) into y[b, t, yc0 + c], plus copy of h[b, t, 0:Ch] to y[..., 0:Ch].
+ * lens (optional int32 [B], NULL = T rows everywhere): utterance b is resampled to lens[b] rows (clamped into
+ * [1, T]; the ratio is L / lens[b], as the utterance alone at T = lens[b]) and its rows t >= lens[b] are zeros */
 typedef struct stzs_prprep_args {
     const float* codes;
     const void* h;
     void* y;
     int64_t ldc, bsc, ldh, bsh, ldy, bsy;
     int32_t B, L, T, c0, Cs, Ch, yc0, f32; /* f32 = 1: h and y fp32 (precise mode), 0: bf16 */
+    const int32_t* lens;
 } stzs_prprep_args;
 int stzs_predictor_prep(const stzs_prprep_args* a, void* stream);
 
-/* durations: round(sum_j sigmoid(logit_j)) (serial fp32 sum), clamp >= 1; override if given */
+/* durations: round(sum_j sigmoid(logit_j)) (serial fp32 sum), clamp >= 1; override if given.
+ * lens (optional int32 [B], NULL = none): dur = 0 and dsum = 0 for t >= lens[b] (clamped into [1, T]), whatever
+ * override_dur holds there -- the padding tokens of a ragged batch take no frames */
 typedef struct stzs_dur_args {
     const float* logits;
     const int32_t* override_dur;
@@ -360,6 +382,7 @@ typedef struct stzs_dur_args {
     float* dsum;
     int64_t ldl, bsl;
     int32_t B, T, nbins, pad_i;
+    const int32_t* lens;
 } stzs_dur_args;
 int stzs_durations(const stzs_dur_args* a, void* stream);
 
@@ -555,12 +578,16 @@ int stzs_state_init(float* x, const float* eps, int B, int N, int cfg, float sig
 /* y[b, c] = mean_l x[b, l, c0 + c]  (pooled style / prompt vectors), f32 */
 int stzs_mean_rows(const float* x, float* y, int B, int L, int64_t ldx, int64_t bsx, int c0,
                    int C, int64_t ldy, void* stream);
-/* generic strided 2-D copy with dtype conversion: R rows x C cols (row r of batch b) */
+/* generic strided 2-D copy with dtype conversion: R rows x C cols (row r of batch b).
+ * dst_row_off (optional int32 [B], NULL = 0): block b is written dst_row_off[b] rows further down,
+ * y[b * bsy + (dst_row_off[b] + r) * ldy + c]; the caller sizes y for the largest offset (a negative one is
+ * taken as 0) */
 typedef struct stzs_copy_args {
     const void* x;
     void* y;
     int64_t ldx, bsx, ldy, bsy;
     int32_t B, R, C, in_dtype, out_dtype, pad_i;
+    const int32_t* dst_row_off;
 } stzs_copy_args;
 int stzs_copy2d(const stzs_copy_args* a, void* stream);
 /* token embedding gather: y[b, t, :] = emb[tok[b, t], :] (f32 table -> bf16 rows) */
@@ -568,6 +595,10 @@ int stzs_embed(const int32_t* tok, const float* emb, void* y, int B, int T, int 
                void* stream);
 /* precise mode: fp32 embedding rows */
 int stzs_embed_f32(const int32_t* tok, const float* emb, float* y, int B, int T, int D, int64_t ldy, void* stream);
+/* ragged batch: as stzs_embed (out_dtype = STZS_BF16) / stzs_embed_f32 (STZS_F32) for t < lens[b] (int32 [B],
+ * clamped into [1, T]); rows t >= lens[b] are written as zeros and their tokens are not read */
+int stzs_embed_lens(const int32_t* tok, const float* emb, void* y, const int32_t* lens, int B, int T, int D,
+                    int64_t ldy, int out_dtype, void* stream);
 
 /* ======================================================================================================
  * Generic tensor-descriptor entry points (SURVEY.md §8(b) "C-ABI"): one per hot-path operator of §8(a),

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void attn_x3(const stzs_attn_args a) {
     const float* K = reinterpret_cast<const float*>(a.k) + r * a.bsk + h * DH;
     const float* V = reinterpret_cast<const float*>(a.v) + r * a.bsv + h * DH;
     const float scale = 1.f / sqrtf((float)DH);
+    const int Lk = a.lk_rows ? min(max(a.lk_rows[r], 1), a.Lk) : a.Lk;  // this row's keys (as attn_body.hpp)
     auto split8 = [](const float* f, bf16x8& hi, bf16x8& lo) {
         uint4 hp = pack8(f);
         float hf[8], lf[8];
@@ -64,11 +65,11 @@ __global__ __launch_bounds__(256) void attn_x3(const stzs_attn_args a) {
         m[i] = -INFINITY;
         l[i] = 0.f;
     }
-    for (int c0 = 0; c0 < a.Lk; c0 += KC) {
+    for (int c0 = 0; c0 < Lk; c0 += KC) {
         __syncthreads();
         for (int i = tid; i < KC * (DH / 8); i += 256) {
             const int kr = i / (DH / 8), cv = i - kr * (DH / 8);
-            const bool ok = c0 + kr < a.Lk;
+            const bool ok = c0 + kr < Lk;
             const int kk = ok ? c0 + kr : 0;
             float kf[8], vf[8];
             load8(K + (long)kk * a.ldk + cv * 8, kf);
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void attn_x3(const stzs_attn_args a) {
             mx[i] = -INFINITY;
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                const bool ok = c0 + nt * 16 + (lane & 15) < a.Lk;
+                const bool ok = c0 + nt * 16 + (lane & 15) < Lk;
                 s[nt][i] = ok ? s[nt][i] * scale : -INFINITY;
                 mx[i] = fmaxf(mx[i], s[nt][i]);
             }

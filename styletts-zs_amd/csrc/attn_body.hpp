@@ -90,6 +90,9 @@ STZS_DEV void attn_unit(const stzs_attn_args& a, long r, int h, int qb0, unsigne
     const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + r * a.bsk + h * DH;
     const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + r * a.bsv + h * DH;
     const float scale = 1.f / sqrtf((float)DH);
+    // this row's key count (stzs_attn_args.lk_rows, clamped into [1, Lk]; r is uniform per workgroup, so the chunk
+    // loop and its barriers stay uniform): keys at or beyond it are never loaded
+    const int Lk = a.lk_rows ? min(max(a.lk_rows[r], 1), a.Lk) : a.Lk;
 
     bf16x8 qf[NKS];
     {
@@ -119,7 +122,7 @@ STZS_DEV void attn_unit(const stzs_attn_args& a, long r, int h, int qb0, unsigne
         for (int j = 0; j < NLD; ++j) {
             const int i = tid + j * 256;
             const int kr = i / (DH / 8), cv = i - kr * (DH / 8);
-            const bool ok = c0 + kr < a.Lk;
+            const bool ok = c0 + kr < Lk;
             const int kk = ok ? c0 + kr : 0;
             pk[j] = LD::ld(K, (long)kk * a.ldk + cv * 8);
             pv[j] = LD::ld(V, (long)kk * a.ldv + cv * 8);
@@ -127,7 +130,7 @@ STZS_DEV void attn_unit(const stzs_attn_args& a, long r, int h, int qb0, unsigne
         }
     };
     load_chunk(0);
-    for (int c0 = 0; c0 < a.Lk; c0 += KC) {
+    for (int c0 = 0; c0 < Lk; c0 += KC) {
         __syncthreads();
         // stage K and V rows for keys [c0, c0 + KC) from the registers (both row-major: V's PV fragments come from
         // transposed reads, r06 -- it was a scalar transposing store), then start the next chunk's loads
@@ -138,7 +141,7 @@ STZS_DEV void attn_unit(const stzs_attn_args& a, long r, int h, int qb0, unsigne
             *reinterpret_cast<uint4*>(Ks + kr * KP + cv * 8) = pk[j];
             *reinterpret_cast<uint4*>(Vs + kr * VP + cv * 8) = pv[j];
         }
-        if (c0 + KC < a.Lk) load_chunk(c0 + KC);
+        if (c0 + KC < Lk) load_chunk(c0 + KC);
         __syncthreads();
         // S = Q K^T for 16 queries x 64 keys
         f32x4 s[4];
@@ -161,7 +164,7 @@ STZS_DEV void attn_unit(const stzs_attn_args& a, long r, int h, int qb0, unsigne
             mx[i] = -INFINITY;
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                const bool ok = c0 + nt * 16 + (lane & 15) < a.Lk;
+                const bool ok = c0 + nt * 16 + (lane & 15) < Lk;
                 s[nt][i] = ok ? s[nt][i] * scale : -INFINITY;
                 mx[i] = fmaxf(mx[i], s[nt][i]);
             }

@@ -344,7 +344,7 @@ static int plain_launch(const stzs_conv_args* a, hipStream_t s) {
 extern "C" int stzs_ln_linear(const stzs_conv_args* a, const stzs_rowln_args* ln, void* stream) {
     if (!a || !a->w || !a->y) return STZS_EINVAL;
     if (!ln) return plain_launch(a, reinterpret_cast<hipStream_t>(stream));
-    if (!ln->x) return STZS_EINVAL;
+    if (!ln->x || ln->lens) return STZS_EINVAL;  // (the ragged mask is stzs_row_layernorm's only)
     const bool lin = a->ks == 1 && a->stride == 1 && a->pad == 0 && a->ups == 0 && a->T_in == a->T_out &&
                      a->pro_mode == STZS_PRO_NONE && a->pro_act == STZS_ACT_NONE && !a->stat_part && !a->x_scale &&
                      !a->res && !a->gate && a->splitk <= 1;

@@ -28,6 +28,10 @@
 // (one slab row = hi[H] | lo[H]), W_hh^T as hi and lo fragments, the recurrent product is
 // h_lo W_hi + h_hi W_lo + h_hi W_hi on the same MFMAs (~fp32 accuracy), the gates use libm expf / tanhf,
 // and y is written in fp32.
+// RAGGED batches (stzs_lstm_args.lens): at a step whose position t is at or beyond an utterance's length the cell
+// update runs as ever and its c and h are then replaced by zeros with selects (no divergence around the DPP gathers,
+// no change to the exchange, the step count or the barriers): the utterance publishes h = 0, stores y = 0, and its
+// reverse recurrence reaches its own last row from the zero state -- the bits of that utterance alone at T = lens[b].
 #include "common.hpp"
 
 namespace {
@@ -128,6 +132,10 @@ __global__ __launch_bounds__(512, 1) void lstm_xchg(const stzs_lstm_args a0, con
     const bool cvalid = crow < nrows;
     const int cb = b0 + (cvalid ? crow : 0);
     float c[CPT];
+    // ragged batch: the length of this thread's utterance, clamped into [1, T] (a predicate only, never an address)
+    // -- of its cell row in the counter form, of its lane's row in the tagged form
+    const int clen = a.lens ? min(max(a.lens[cb], 1), a.T) : a.T;
+    const int tlen = a.lens ? min(max(a.lens[b0 + min(tid >> 7, nrows - 1)], 1), a.T) : a.T;
     float c1 = 0.f;  // the tagged (batch <= 2) cell map's one cell per quad
 #pragma unroll
     for (int j = 0; j < CPT; ++j) c[j] = 0.f;
@@ -251,7 +259,9 @@ __global__ __launch_bounds__(512, 1) void lstm_xchg(const stzs_lstm_args a0, con
                 const float act = g == 2 ? fast_tanh(pre) : fast_sigmoid(pre);
                 const float fg = dpp_f<0x55>(act), gt = dpp_f<0xAA>(act), og = dpp_f<0xFF>(act);  // quad lanes 1, 2, 3
                 c1 = cell_c(act, fg, gt, c1);  // (meaningful in the g = 0 lane)
-                const float h = cell_h(og, c1);
+                const bool keep = t < tlen;    // (one row per 128 lanes: the h1 gather below stays inside it)
+                c1 = keep ? c1 : 0.f;
+                const float h = keep ? cell_h(og, c1) : 0.f;
                 // unit u + 1's h (its g = 0 lane, 4 lanes up -- inside the same 16-lane row for the even units that
                 // publish): DPP row_shl:4 instead of a ds_bpermute round trip
                 const float h1 = dpp_f<0x104>(h);
@@ -283,6 +293,7 @@ __global__ __launch_bounds__(512, 1) void lstm_xchg(const stzs_lstm_args a0, con
                 c[j] = cell_c(ig, fg, fast_tanh(gg), c[j]);
                 hv[j] = cell_h(og, c[j]);
             }
+            if (t >= clen) c[j] = hv[j] = 0.f;  // ragged batch: past this utterance's end (a select per cell)
         }
         const uint2 hb = make_uint2(pack2bf(hv[0], hv[1]), pack2bf(hv[2], hv[3]));
         if (cvalid) {

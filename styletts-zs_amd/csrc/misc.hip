@@ -84,7 +84,8 @@ __global__ void copy_kernel(const stzs_copy_args a) {
     const long rr = (i / a.C) % a.R;
     const long b = i / ((long)a.C * a.R);
     const float v = DT<TI>::ld(reinterpret_cast<const TI*>(a.x) + b * a.bsx + rr * a.ldx + c);
-    DT<TO>::st(reinterpret_cast<TO*>(a.y) + b * a.bsy + rr * a.ldy + c, v);
+    const long ro = a.dst_row_off ? max(a.dst_row_off[b], 0) : 0;  // (the caller sizes y for its offsets)
+    DT<TO>::st(reinterpret_cast<TO*>(a.y) + b * a.bsy + (ro + rr) * a.ldy + c, v);
 }
 
 template <typename TO>
@@ -94,6 +95,17 @@ __global__ void embed_kernel(const int32_t* tok, const float* emb, TO* y, int B,
     const float* e = emb + (long)id * D;
     TO* o = y + ((long)b * T + t) * ldy;
     for (int c = threadIdx.x; c < D; c += 256) DT<TO>::st(o + c, e[c]);
+}
+
+// ragged batch: rows t >= lens[b] (clamped into [1, T]) are zeros, their tokens are not read
+template <typename TO>
+__global__ void embed_lens_kernel(const int32_t* tok, const float* emb, TO* y, const int32_t* lens, int B, int T,
+                                  int D, long ldy) {
+    const int t = blockIdx.x, b = blockIdx.y;
+    const bool keep = t < min(max(lens[b], 1), T);  // uniform per workgroup
+    const float* e = emb + (long)(keep ? tok[(long)b * T + t] : 0) * D;
+    TO* o = y + ((long)b * T + t) * ldy;
+    for (int c = threadIdx.x; c < D; c += 256) DT<TO>::st(o + c, keep ? e[c] : 0.f);
 }
 
 inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
@@ -203,6 +215,23 @@ extern "C" int stzs_embed_f32(const int32_t* tok, const float* emb, float* y, in
     if (B <= 0 || T <= 0 || D <= 0) return STZS_ESHAPE;
     hipLaunchKernelGGL(embed_kernel<float>, dim3(T, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tok, emb,
                        y, B, T, D, (long)ldy);
+    STZS_LAUNCH_CHECK();
+    return STZS_OK;
+}
+
+extern "C" int stzs_embed_lens(const int32_t* tok, const float* emb, void* y, const int32_t* lens, int B, int T,
+                               int D, int64_t ldy, int out_dtype, void* stream) {
+    if (!tok || !emb || !y || !lens) return STZS_EINVAL;
+    if (B <= 0 || T <= 0 || D <= 0) return STZS_ESHAPE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (out_dtype == STZS_BF16)
+        hipLaunchKernelGGL(embed_lens_kernel<bf16_t>, dim3(T, B), dim3(256), 0, s, tok, emb,
+                           reinterpret_cast<bf16_t*>(y), lens, B, T, D, (long)ldy);
+    else if (out_dtype == STZS_F32)
+        hipLaunchKernelGGL(embed_lens_kernel<float>, dim3(T, B), dim3(256), 0, s, tok, emb,
+                           reinterpret_cast<float*>(y), lens, B, T, D, (long)ldy);
+    else
+        return STZS_EDTYPE;
     STZS_LAUNCH_CHECK();
     return STZS_OK;
 }

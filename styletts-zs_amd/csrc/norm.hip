@@ -243,6 +243,7 @@ extern "C" int stzs_row_layernorm(const stzs_rowln_args* a, void* stream) {
         return STZS_ESHAPE;
     if ((a->G && (a->gs % 8 || !stzs_aligned(a->G, 32))) || (a->Bt && (a->bs % 8 || !stzs_aligned(a->Bt, 32))))
         return STZS_ESHAPE;  // modulation rows are read as 32-B vectors
+    if (a->lens && (a->T <= 0 || a->R % a->T)) return STZS_ESHAPE;  // ragged mask: R = blocks of T rows
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 g((a->R + 3) / 4);
     if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16)

@@ -11,13 +11,21 @@ __global__ __launch_bounds__(256) void pr_prep(const stzs_prprep_args a) {
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     TT* Y = reinterpret_cast<TT*>(a.y) + (long)b * a.bsy + (long)t * a.ldy;
     const TT* Hs = reinterpret_cast<const TT*>(a.h) + (long)b * a.bsh + (long)t * a.ldh;
+    // ragged batch: this utterance's own row count (clamped into [1, T]; uniform per workgroup)
+    const int Tb = a.lens ? min(max(a.lens[b], 1), a.T) : a.T;
+    if (t >= Tb) {  // a pad row: zeros over the text and the style columns
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int v = tid; v < a.Ch / 8; v += 256) store8(Y + v * 8, z);
+        for (int c = tid; c < a.Cs; c += 256) DT<TT>::st(Y + a.yc0 + c, 0.f);
+        return;
+    }
     for (int v = tid; v < a.Ch / 8; v += 256) {
         float f[8];
         load8(Hs + v * 8, f);
         store8(Y + v * 8, f);
     }
     // torch upsample_linear1d, align_corners=False (area_pixel_compute_source_index)
-    const float ratio = (float)a.L / (float)a.T;
+    const float ratio = (float)a.L / (float)Tb;
     float src = ratio * ((float)t + 0.5f) - 0.5f;
     if (src < 0.f) src = 0.f;
     const int i0 = (int)src;
@@ -46,10 +54,13 @@ __global__ __launch_bounds__(256) void dur_kernel(const stzs_dur_args a) {
         for (int u = 0; u < 8; ++u) acc = __fadd_rn(acc, 1.f / (1.f + expf(-v[u])));
     }
     for (; j < a.nbins; ++j) acc = __fadd_rn(acc, 1.f / (1.f + expf(-L[j])));
-    if (a.dsum) a.dsum[i] = acc;
+    // ragged batch: a padding token (t >= lens[b], clamped into [1, T]) takes no frames, forced or not
+    const bool keep = !a.lens || t < min(max(a.lens[b], 1), a.T);
+    if (a.dsum) a.dsum[i] = keep ? acc : 0.f;
     int d = (int)rintf(acc);
     if (d < 1) d = 1;
-    a.dur[i] = a.override_dur ? a.override_dur[i] : d;
+    if (a.override_dur) d = a.override_dur[i];
+    a.dur[i] = keep ? d : 0;
 }
 
 __global__ __launch_bounds__(256) void align_kernel(const stzs_align_args a) {

@@ -74,9 +74,10 @@ STZS_DEV void ln_row_out(const stzs_rowln_args& a, int lane, const float (&v)[MA
 }
 
 // normalise, modulate, activate and store row r whose values are in registers (lane holds the 8-value
-// vectors lane + 64 i)
+// vectors lane + 64 i); keep = false (wave-uniform: a pad row of a ragged batch, stzs_rowln_args.lens) stores
+// exact zeros instead
 template <typename TO, int MAXV>
-STZS_DEV void ln_row_finish(const stzs_rowln_args& a, long r, int lane, float (&v)[MAXV][8]) {
+STZS_DEV void ln_row_finish(const stzs_rowln_args& a, long r, int lane, float (&v)[MAXV][8], bool keep = true) {
     const int nv = a.C >> 3;
     TO* Y = reinterpret_cast<TO*>(a.y) + r * a.ldy;
     // (modulation rows as 32-B vectors: gs, bs and the bases are multiples of 8 floats, checked on the host)
@@ -84,7 +85,10 @@ STZS_DEV void ln_row_finish(const stzs_rowln_args& a, long r, int lane, float (&
     float amax = 0.f, mu, rstd, g[MAXV][8], bt[MAXV][8];
     ln_row_stats<MAXV>(a, lane, v, mu, rstd);
     ln_mod_load<MAXV>(a, r / a.gdiv, lane, g, bt);
-    ln_row_out<MAXV>(a, lane, v, mu, rstd, g, bt, [&](int i, int vi, const float* o) {
+    ln_row_out<MAXV>(a, lane, v, mu, rstd, g, bt, [&](int i, int vi, const float* oa) {
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = keep ? oa[j] : 0.f;
         if constexpr (F8) {  // (slot i was consumed above: overwritten with its result)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -108,7 +112,12 @@ STZS_DEV void row_ln_one(const stzs_rowln_args& a, long r, int lane) {
 #pragma unroll
     for (int i = 0; i < MAXV; ++i)
         if (lane + i * 64 < nv) load8(X + (lane + i * 64) * 8, v[i]);
-    ln_row_finish<TO, MAXV>(a, r, lane, v);
+    bool keep = true;
+    if (a.lens) {  // ragged mask: the length clamped into [1, T], used as a predicate only
+        const long b = r / a.T;
+        keep = (int)(r - b * a.T) < min(max(a.lens[b], 1), a.T);
+    }
+    ln_row_finish<TO, MAXV>(a, r, lane, v, keep);
 }
 
 // quantise a register-resident row (lane holds vectors lane + 64 i) to e4m3fn with one row scale

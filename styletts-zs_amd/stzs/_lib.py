@@ -61,7 +61,8 @@ class RowLNArgs(C.Structure):
     _fields_ = [("x", vp), ("y", vp), ("G", vp), ("Bt", vp),
                 ("ldx", i64), ("ldy", i64), ("gs", i64), ("bs", i64),
                 ("R", i32), ("C", i32), ("gdiv", i32), ("in_dtype", i32), ("out_dtype", i32), ("act", i32),
-                ("gadd", f32), ("eps", f32), ("slope", f32), ("pad_f", f32), ("y_scale", vp)]
+                ("gadd", f32), ("eps", f32), ("slope", f32), ("pad_f", f32), ("y_scale", vp),
+                ("lens", vp), ("T", i32), ("pad_t", i32)]  # lens: optional ragged mask over blocks of T rows
 
 
 class QuantArgs(C.Structure):
@@ -71,14 +72,16 @@ class QuantArgs(C.Structure):
 class AttnArgs(C.Structure):
     _fields_ = [("q", vp), ("k", vp), ("v", vp), ("o", vp)] + \
                [(n, i64) for n in ("ldq", "ldk", "ldv", "ldo", "bsq", "bsk", "bsv", "bso")] + \
-               [(n, i32) for n in ("R", "Lq", "Lk", "heads", "dh", "precise")]
+               [(n, i32) for n in ("R", "Lq", "Lk", "heads", "dh", "precise")] + \
+               [("lk_rows", vp)]  # optional int32 [R]: keys per row
 
 
 class LstmArgs(C.Structure):
     _fields_ = [("gx", vp), ("whhT", vp), ("y", vp), ("xchg", vp), ("sync", vp),
                 ("ldg", i64), ("bsg", i64), ("ldy", i64), ("bsy", i64),
                 ("B", i32), ("T", i32), ("H", i32), ("ndir", i32),
-                ("status", vp), ("spin_limit", C.c_uint32), ("precise", C.c_uint32)]
+                ("status", vp), ("spin_limit", C.c_uint32), ("precise", C.c_uint32),
+                ("lens", vp)]  # optional int32 [B]: steps per utterance
 
 
 STATUS_LSTM_TIMEOUT = 1  # include/stzs.h STZS_STATUS_LSTM_TIMEOUT
@@ -87,12 +90,12 @@ STATUS_LSTM_TIMEOUT = 1  # include/stzs.h STZS_STATUS_LSTM_TIMEOUT
 class PrPrepArgs(C.Structure):
     _fields_ = [("codes", vp), ("h", vp), ("y", vp)] + \
                [(n, i64) for n in ("ldc", "bsc", "ldh", "bsh", "ldy", "bsy")] + \
-               [(n, i32) for n in ("B", "L", "T", "c0", "Cs", "Ch", "yc0", "f32")]
+               [(n, i32) for n in ("B", "L", "T", "c0", "Cs", "Ch", "yc0", "f32")] + [("lens", vp)]
 
 
 class DurArgs(C.Structure):
     _fields_ = [("logits", vp), ("override_dur", vp), ("dur", vp), ("dsum", vp),
-                ("ldl", i64), ("bsl", i64), ("B", i32), ("T", i32), ("nbins", i32), ("pad_i", i32)]
+                ("ldl", i64), ("bsl", i64), ("B", i32), ("T", i32), ("nbins", i32), ("pad_i", i32), ("lens", vp)]
 
 
 class AlignArgs(C.Structure):
@@ -165,7 +168,7 @@ class VqArgs(C.Structure):
 
 class CopyArgs(C.Structure):
     _fields_ = [("x", vp), ("y", vp)] + [(n, i64) for n in ("ldx", "bsx", "ldy", "bsy")] + \
-               [(n, i32) for n in ("B", "R", "C", "in_dtype", "out_dtype", "pad_i")]
+               [(n, i32) for n in ("B", "R", "C", "in_dtype", "out_dtype", "pad_i")] + [("dst_row_off", vp)]
 
 
 class Tensor(C.Structure):
@@ -220,7 +223,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
            "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_code_quantize",
            "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler",
-           "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_embed", "stzs_embed_f32", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
+           "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
 
 _lib = None
@@ -286,6 +289,7 @@ def load():
         "stzs_copy2d": ([P(CopyArgs), vp], i32),
         "stzs_embed": ([vp, vp, vp, i32, i32, i32, i64, vp], i32),
         "stzs_embed_f32": ([vp, vp, vp, i32, i32, i32, i64, vp], i32),
+        "stzs_embed_lens": ([vp, vp, vp, vp, i32, i32, i32, i64, i32, vp], i32),
         "stzs_pack_conv_size": ([i32, i32, i32, i32, i32], C.c_size_t),
         "stzs_pack_conv": ([vp, i32, i32, i32, i32, i32, vp], i32),
         "stzs_pack_lstm": ([vp] * 8 + [i32, i32, vp, vp, vp], i32),

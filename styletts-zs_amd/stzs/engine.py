@@ -209,6 +209,20 @@ class Act:
         return Act(self.t[b0:b0 + nb], self.c0, self.C)
 
 
+def check_text_lens(text_lens, B: int, T: int) -> torch.Tensor:
+    """host-side check of a ragged batch's per-row text lengths -> int32 [B] host tensor.  text_lens: a host
+    tensor or a sequence of B integers, each in [1, T] (T the padded width); anything else raises ValueError.
+    (A device tensor is never checked -- that would be a sync -- the kernels clamp what they read.)"""
+    t = torch.as_tensor(text_lens)
+    if t.device.type != "cpu":
+        raise ValueError("check_text_lens takes host lengths")
+    if t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"text_lens must be {B} integers (one per row), got {tuple(t.shape)} {t.dtype}")
+    if B and (int(t.min()) < 1 or int(t.max()) > T):
+        raise ValueError(f"text_lens must lie in [1, {T}] (the padded width), got {t.tolist()}")
+    return t.to(torch.int32)
+
+
 def sigma_schedule(spec: Spec, steps: int):
     """Distilled pins 1: [smax, 0], 2: [smax, 0.5, 0]; otherwise Karras(rho) + trailing 0 (a1)."""
     if steps == 1:
@@ -786,9 +800,12 @@ class StyleTTSZS:
         return _StatPtr(ref, 0), _StatPtr(ref, 1), Cc
 
     def rowln(self, x: Act, y: Act, *, G=None, gs=0, Bt=None, bs=0, gdiv=1, gadd=1.0, act=L.ACT_NONE, slope=0.0,
-              R=None, y_scale=None, what="rowln"):
+              R=None, y_scale=None, lens=None, what="rowln"):
+        """lens (int32 [B] device tensor): rows t >= lens[b] of the x.T-row blocks are stored as zeros"""
         a = self._ln_args(x, y, G=G, gs=gs, Bt=Bt, bs=bs, gdiv=gdiv, gadd=gadd, y_scale=y_scale)
         a.act, a.slope = act, slope
+        if lens is not None:
+            a.lens, a.T = lens.data_ptr(), x.T
         if R is not None:
             a.R = R
         assert x.ld * x.T == x.bs and y.ld * y.T == y.bs
@@ -812,28 +829,32 @@ class StyleTTSZS:
         a.precise = int(q.t.dtype == torch.float32)  # fp32 operands: the fp32 attention kernel
         return a
 
-    def attention(self, q: Act, k: Act, v: Act, o: Act):
+    def attention(self, q: Act, k: Act, v: Act, o: Act, lk_rows: torch.Tensor = None):
+        """lk_rows (int32 [R] device tensor): row r attends to its first lk_rows[r] keys only"""
         a = self._attn_args(q, k, v, o)
+        if lk_rows is not None:
+            a.lk_rows = lk_rows.data_ptr()
         self._call(self.lib.stzs_attention, a, "attention",
                    cost=(4.0 * a.R * a.heads * a.Lq * a.Lk * a.dh,
                          a.R * (2 * a.Lq + 2 * a.Lk) * a.heads * a.dh * q.t.element_size()))
 
-    def lstm(self, lw, x: Act, y: Act, key):
-        a, cost = self._lstm_args(lw, x, y, key)
+    def lstm(self, lw, x: Act, y: Act, key, lens: torch.Tensor = None):
+        """lens (int32 [B] device tensor): utterance b runs as alone at T = lens[b], y[b, t >= lens[b]] = 0"""
+        a, cost = self._lstm_args(lw, x, y, key, lens=lens)
         self._call(self.lib.stzs_lstm, a, key + ".rec", cost=cost)  # recurrent products + gate rows in, h rows out
         return y
 
     def lstm_pair(self, r0, r1):
-        """two independent recurrences r = (lw, x, y, key) of one shape class in ONE launch (stzs_lstm_pair: side by
-        side on the chip; each output the same bits as its own lstm() call): both input projections, then the
-        paired recurrence on separate exchange state."""
-        a0, c0 = self._lstm_args(*r0)
-        a1, c1 = self._lstm_args(*r1, pair=True)
+        """two independent recurrences r = (lw, x, y, key[, lens]) of one shape class in ONE launch (stzs_lstm_pair:
+        side by side on the chip; each output the same bits as its own lstm() call): both input projections, then
+        the paired recurrence on separate exchange state."""
+        a0, c0 = self._lstm_args(*r0[:4], lens=r0[4] if len(r0) > 4 else None)
+        a1, c1 = self._lstm_args(*r1[:4], pair=True, lens=r1[4] if len(r1) > 4 else None)
         self._call(self.lib.stzs_lstm_pair, a0, r0[3] + ".rec+" + r1[3] + ".rec",
                    cost=(c0[0] + c1[0], c0[1] + c1[1]), b=a1)
         return r0[2], r1[2]
 
-    def _lstm_args(self, lw, x: Act, y: Act, key, pair=False):
+    def _lstm_args(self, lw, x: Act, y: Act, key, pair=False, lens=None):
         """input projection (one MFMA GEMM over all steps) + the recurrence's arguments -> (LstmArgs, cost)"""
         gx = self.act(key + ".gx", x.B, x.T, 8 * lw.H, torch.float32)
         self.conv(lw.ih, x, gx, what=key + ".ih")
@@ -850,6 +871,7 @@ class StyleTTSZS:
         a.ldg, a.bsg, a.ldy, a.bsy = gx.ld, gx.bs, y.ld, y.bs
         a.B, a.T, a.H, a.ndir = x.B, x.T, lw.H, 2
         a.status, a.spin_limit = self.status.data_ptr(), self.lstm_spin_limit
+        a.lens = lens.data_ptr() if lens is not None else None
         # (flops, bytes): recurrent products; gate rows in, h rows out, W_hh once
         return a, (2.0 * x.B * x.T * 2 * 4 * lw.H * lw.H,
                    x.B * x.T * (8 * lw.H * 4 + 2 * lw.H * y.t.element_size()) + 2 * 4 * lw.H * lw.H * 2)
@@ -858,9 +880,11 @@ class StyleTTSZS:
         self._copy_rows(x.ptr, x.ld, x.bs if bsx is None else bsx, y.ptr, y.ld, y.bs, y.B, R, Cn, x.dt, y.dt, "copy2d")
 
     def _copy_rows(self, x: int, ldx: int, bsx: int, y: int, ldy: int, bsy: int, nb: int, R: int, Cn: int, dti, dto,
-                   what="copy_windows"):
-        """stzs_copy2d on raw byte addresses: nb blocks of R rows x Cn columns (source block stride bsx elements)"""
+                   what="copy_windows", row_off: torch.Tensor = None):
+        """stzs_copy2d on raw byte addresses: nb blocks of R rows x Cn columns (source block stride bsx elements);
+        row_off (int32 [nb] device tensor): block b lands row_off[b] rows further down in y"""
         a = L.CopyArgs()
+        a.dst_row_off = row_off.data_ptr() if row_off is not None else None
         a.x, a.y, a.ldx, a.bsx, a.ldy, a.bsy = x, y, ldx, bsx, ldy, bsy
         a.B, a.R, a.C, a.in_dtype, a.out_dtype = nb, R, Cn, dti, dto
         self._call(self.lib.stzs_copy2d, a, what)
@@ -872,24 +896,47 @@ class StyleTTSZS:
         return y
 
     # ------------------------------------------------------------------ front ends
-    def text_encode(self, tokens: torch.Tensor) -> Act:
+    def text_lens(self, text_lens, B: int, T: int):
+        """the per-row text lengths of a ragged batch as an int32 [B] device tensor (None stays None): host lengths
+        are range-checked (check_text_lens) and uploaded, a device tensor is taken as it is -- no sync, so a front
+        given one stays capturable; the kernels clamp what they read into [1, T]."""
+        if text_lens is None:
+            return None
+        if isinstance(text_lens, torch.Tensor) and text_lens.device.type != "cpu":
+            if text_lens.dtype != torch.int32 or tuple(text_lens.shape) != (B,) or not text_lens.is_contiguous():
+                raise ValueError(f"device text_lens must be a contiguous int32 [{B}] tensor")
+            return text_lens
+        host = check_text_lens(text_lens, B, T)
+        dev = self.buf("text_lens", (B,), torch.int32)
+        dev.copy_(host)
+        return dev
+
+    def text_encode(self, tokens: torch.Tensor, text_lens=None) -> Act:
         """tokens int32 [B, T] (device) -> h_txt bf16 [B, T, d_txt] (StyleTTS2 TextEncoder):
         embedding gather, te_layers x (k5 conv on MFMA, LayerNorm + LeakyReLU 0.2), then the BiLSTM
-        (input projection on MFMA + the register-resident exchange recurrence of csrc/lstm.hip)."""
+        (input projection on MFMA + the register-resident exchange recurrence of csrc/lstm.hip).
+        text_lens (DESIGN.md "Ragged text batches"): row b is computed as alone at T = text_lens[b]; the embedding
+        and every LayerNorm store its rows t >= text_lens[b] as zeros -- the zero padding the k5 convs see at a
+        sequence end -- and the BiLSTM resets its state there, so h_txt[b, text_lens[b]:] = 0."""
         S, W = self.spec, self.W
         B, T = tokens.shape
+        lens = self.text_lens(text_lens, B, T)
         e = self.act("te.e", B, T, S.d_txt, self.adt)
         c = self.act("te.c", B, T, S.d_txt, self.adt)
-        emb = self.lib.stzs_embed_f32 if self.adt == torch.float32 else self.lib.stzs_embed
-        self._raw(emb, "embed", tokens.data_ptr(), W.t(W.te_emb).data_ptr(), e.ptr, B, T, S.d_txt, e.ld)
+        if lens is not None:
+            self._raw(self.lib.stzs_embed_lens, "embed", tokens.data_ptr(), W.t(W.te_emb).data_ptr(), e.ptr,
+                      lens.data_ptr(), B, T, S.d_txt, e.ld, e.dt)
+        else:
+            emb = self.lib.stzs_embed_f32 if self.adt == torch.float32 else self.lib.stzs_embed
+            self._raw(emb, "embed", tokens.data_ptr(), W.t(W.te_emb).data_ptr(), e.ptr, B, T, S.d_txt, e.ld)
         for i in range(S.te_layers):
             self.conv(W.te_conv[i], e, c, pad=S.te_kernel // 2, splitk=0 if self.adt == torch.float32 else self.te_splitk,
                       what=f"te.conv{i}")
             g, b = W.te_ln[i]
             self.rowln(c, e, G=W.t(g).data_ptr(), gs=0, Bt=W.t(b).data_ptr(), bs=0, gadd=0.0,
-                       act=L.ACT_LEAKY, slope=0.2, what=f"te.ln{i}")
+                       act=L.ACT_LEAKY, slope=0.2, lens=lens, what=f"te.ln{i}")
         h = self.act("te.h", B, T, S.d_txt, self.adt)
-        return self.lstm(W.te_lstm, e, h, "te.lstm")
+        return self.lstm(W.te_lstm, e, h, "te.lstm", lens=lens)
 
     def log_mel(self, wav: torch.Tensor, dtype=None) -> Act:
         """reference wav fp32 [B, N] (device) -> log-mel [B, N/hop + 1, n_mels]:
@@ -989,9 +1036,10 @@ class StyleTTSZS:
 
     # ------------------------------------------------------------------ (a) style diffusion
     def sample_style(self, h_txt: Act, prompt: torch.Tensor, eps: torch.Tensor, steps: int,
-                     cfg_scale: float = 1.0) -> torch.Tensor:
+                     cfg_scale: float = 1.0, text_lens=None) -> torch.Tensor:
         """a1-a4: Euler sampling over the distilled / Karras sigma schedule with classifier-free guidance.
-        h_txt [B, T, d_txt] bf16, prompt [B, L_s, code] fp32, eps [B, L_s, code] -> codes fp32 [B, L_s, code]."""
+        h_txt [B, T, d_txt] bf16, prompt [B, L_s, code] fp32, eps [B, L_s, code] -> codes fp32 [B, L_s, code].
+        text_lens: row b's cross-attention sees its first text_lens[b] text rows, then the prompt (denoiser_prepare)."""
         S = self.spec
         B = h_txt.B
         cfg = cfg_scale != 1.0
@@ -1001,7 +1049,7 @@ class StyleTTSZS:
             hs = self.act("dn.h_txt", B, h_txt.T, h_txt.C, self.sdt)
             self.copy2d(h_txt, hs, h_txt.T, h_txt.C)
             h_txt = hs
-        st = self.denoiser_prepare(h_txt, prompt, sig[:steps], cfg)
+        st = self.denoiser_prepare(h_txt, prompt, sig[:steps], cfg, text_lens)
         x = self.buf("dn.x", (R, S.L_s, S.code_dim), torch.float32)
         N = S.L_s * S.code_dim
         self._raw(self.lib.stzs_state_init, "state_init", x.data_ptr(), eps.data_ptr(), B, N, int(cfg), float(sig[0]))
@@ -1022,28 +1070,52 @@ class StyleTTSZS:
         self.denoiser_step(st, 0, Act(x), D)
         return D.t
 
-    def denoiser_prepare(self, h_txt: Act, prompt: torch.Tensor, sigmas, cfg: bool) -> dict:
+    def denoiser_prepare(self, h_txt: Act, prompt: torch.Tensor, sigmas, cfg: bool, text_lens=None) -> dict:
         """step-invariant part of a sampling run: the cross-attention context [ctx_txt(h) ; ctx_prm(prompt | null)]
         and its per-layer K/V, the pooled prompt, and the conditioning of EVERY sigma at once (rows s * R + r):
-        adaLN-single input, its two projections and the per-layer expansion -> 5 launches instead of 5 per NFE."""
+        adaLN-single input, its two projections and the per-layer expansion -> 5 launches instead of 5 per NFE.
+        text_lens (ragged batch): the text context is written over all T rows, row r's prompt (null) context is
+        packed behind its own text rows -- ctx[r, len_r : len_r + L_s] -- and its cross-attention reads
+        lk_rows[r] = len_r + L_s keys: the keys of that row alone, in the same order.  Context / K / V rows past
+        them are computed and never read."""
         S, W = self.spec, self.W
         B, T = h_txt.B, h_txt.T
         R = 2 * B if cfg else B
         Ls, d, cd = S.L_s, S.dn_d, S.code_dim
         Lc = T + Ls
         steps = len(sigmas)
+        lens = self.text_lens(text_lens, B, T)
+        lk = None
         ctx = self.act("dn.ctx", R, Lc, d, self.sdt)
         # ctx_txt rows: the conv writes T rows per utterance into a buffer of Lc rows per utterance
         self._conv_rows(W.dn_ctx_txt, h_txt, ctx.t, 0, 0, "dn.ctx_txt")
         pa = Act(prompt)
-        self._conv_rows(W.dn_ctx_prm, pa, ctx.t, 0, T, "dn.ctx_prm")
+        esz = ctx.t.element_size()
+        if lens is None:
+            self._conv_rows(W.dn_ctx_prm, pa, ctx.t, 0, T, "dn.ctx_prm")
+        else:  # the prompt context beside the buffer, then each row's copy to behind its own text rows
+            cp = self.act("dn.ctx_prm", B, Ls, d, self.sdt)
+            self.conv(W.dn_ctx_prm, pa, cp, what="dn.ctx_prm")
+            # the copies' destination row offsets: the lengths clamped into [1, T] on the device (a device
+            # text_lens is not checked on the host: whatever it holds, the copies stay inside ctx), and the key
+            # counts from them -- stream-ordered device ops into cached buffers, capturable
+            lens = torch.clamp(lens, 1, T, out=self.buf("dn.row_off", (B,), torch.int32))
+            lk = self.buf("dn.lk_rows", (R,), torch.int32)
+            for r0 in range(0, R, B):
+                torch.add(lens, Ls, out=lk[r0:r0 + B])
+            self._copy_rows(cp.ptr, cp.ld, cp.bs, ctx.ptr, ctx.ld, ctx.bs, B, Ls, d, cp.dt, ctx.dt, "ctx_prm_pack",
+                            row_off=lens)
         if cfg:
             self._conv_rows(W.dn_ctx_txt, h_txt, ctx.t, B, 0, "dn.ctx_txt.u")
             f32 = self.sdt == torch.float32
             nul = Act(W.t(W.dn_ctx_null32 if f32 else W.dn_ctx_null)[None])
             dst = Act(ctx.t[B:]).rows(0, B)
-            self._copy_rows(nul.ptr, d, 0, dst.t.data_ptr() + T * ctx.ld * ctx.t.element_size(), ctx.ld, Lc * ctx.ld,
-                            B, Ls, d, nul.dt, ctx.dt, "ctx_null")
+            if lens is None:
+                self._copy_rows(nul.ptr, d, 0, dst.t.data_ptr() + T * ctx.ld * esz, ctx.ld, Lc * ctx.ld,
+                                B, Ls, d, nul.dt, ctx.dt, "ctx_null")
+            else:
+                self._copy_rows(nul.ptr, d, 0, dst.t.data_ptr(), ctx.ld, Lc * ctx.ld, B, Ls, d, nul.dt, ctx.dt,
+                                "ctx_null", row_off=lens)
         pm = self.mean_rows(prompt, 0, cd, "dn.pm")
         pool = self.buf("dn.pool", (R, d), torch.float32)
         self.conv(W.dn_pool, Act(pm[:, None]), Act(pool[:B, None]), rows=self._rows_z(W.dn_pool), what="dn.pool")
@@ -1086,7 +1158,7 @@ class StyleTTSZS:
                   modx.data_ptr(), steps * R, d, 6, S.dn_layers, 0b010010)
         self._raw(self.lib.stzs_adaln_expand, "adaln_expand.f", fmod.data_ptr(), None, fmodx.data_ptr(), steps * R, d,
                   2, 1, 0b10)
-        return dict(R=R, sig=list(sigmas), kv=kv, modx=modx, fmodx=fmodx)
+        return dict(R=R, sig=list(sigmas), kv=kv, modx=modx, fmodx=fmodx, lk=lk)
 
     def denoiser_step(self, st: dict, i: int, xa: Act, D: Act):
         """one NFE: D = c_skip x + c_out F(c_in x, sigma_i) for the R rows of xa, with the conditioning prepared
@@ -1147,7 +1219,7 @@ class StyleTTSZS:
             self.conv(lw["o" + sfx], xo, h, res=h, gate=mb + 2 * d * fsz, gate_bs=6 * d, x_scale=so,
                       post_ln=post(3 * l + 1), splitk=sk.get("o", 0), rows=rk.get("o", 0), what="sa_o")
             self.conv(lw["q" + sfx], ain, q, x_scale=sin, splitk=sk.get("q", 0), rows=rk.get("q", 0),
-                      pre_ln=pre(3 * l + 1), attn=(q, kv[l].sl(0, d), kv[l].sl(d, d), o), what="ca_q")
+                      pre_ln=pre(3 * l + 1), attn=(q, kv[l].sl(0, d), kv[l].sl(d, d), o, st.get("lk")), what="ca_q")
             if f8:
                 self.quant(o, o8, s_o)
             self.conv(lw["co" + sfx], xo, h, res=h, x_scale=so, post_ln=post(3 * l + 2), splitk=sk.get("co", 0),
@@ -1183,30 +1255,38 @@ class StyleTTSZS:
         self.conv(cw, x, view, T_out=T, what=what)
 
     # ------------------------------------------------------------------ (b) prosody predictor
-    def predict_prosody(self, h_txt: Act, codes: torch.Tensor, durations=None, n_frames=None):
+    def predict_prosody(self, h_txt: Act, codes: torch.Tensor, durations=None, n_frames=None, text_lens=None):
         """durations: optional int tensor [B, T_txt] (host or device); n_frames: their per-utterance sum if
-        known (avoids the device->host sync, e.g. under graph capture).  Returns dict of device tensors."""
+        known (avoids the device->host sync, e.g. under graph capture).  Returns dict of device tensors.
+        text_lens: ragged text rows (duration_encoder); the padding tokens get duration 0 and the alignment never
+        references them, so the batch still only has to share its frame count."""
+        text_lens = self.text_lens(text_lens, h_txt.B, h_txt.T)
         if self.dur_overlap and durations is not None and (n_frames is not None or durations.device.type == "cpu"):
             # the alignment reads the given durations, so the duration LSTM no longer gates the frame branch: it
             # runs in ONE launch with the shared F0/N LSTM (stzs_lstm_pair), its projection and the durations kernel
             # after the F0/N branches -- every output the same bits as the sequential order
-            d, ov = self.duration_encoder(h_txt, codes, durations)
+            d, ov = self.duration_encoder(h_txt, codes, durations, text_lens)
             if n_frames is not None:
                 T40 = int(n_frames)
             else:
-                tot = durations.to(torch.int64).sum(1)
+                tot = durations.to(torch.int64)
+                if text_lens is not None:  # (forced durations of padding tokens do not count: the kernel zeroes them)
+                    tot = tot * (torch.arange(h_txt.T)[None] < text_lens.cpu()[:, None])
+                tot = tot.sum(1)
                 assert int(tot.min()) == int(tot.max()), \
                     "one batch must share its total frame count (stzs.scheduler.BucketScheduler groups by it)"
                 T40 = int(tot[0])
-            pro = self.prosody_frames(h_txt, codes, d, ov, T40, pair_dur=True)
-            du = self.duration_head(d, ov, hd=pro.pop("_hd"))
+            if text_lens is not None:  # the alignment reads the durations with the padding tokens' zeroed
+                ov = self._mask_durations(ov, text_lens)
+            pro = self.prosody_frames(h_txt, codes, d, ov, T40, pair_dur=True, text_lens=text_lens)
+            du = self.duration_head(d, ov, hd=pro.pop("_hd"), text_lens=text_lens)
             pro.update(du, dur=du["dur"])
             return pro
-        du = self.predict_durations(h_txt, codes, durations)
+        du = self.predict_durations(h_txt, codes, durations, text_lens)
         if n_frames is not None:
             T40 = int(n_frames)
         else:
-            if durations is not None and durations.device.type == "cpu":
+            if durations is not None and durations.device.type == "cpu" and text_lens is None:
                 tot = durations.to(torch.int64).sum(1)
             else:
                 tot = du["dur"].to(torch.int64).sum(1).cpu()  # host sync: the frame count sizes every later buffer
@@ -1215,17 +1295,30 @@ class StyleTTSZS:
             T40 = int(tot[0])
         return self.prosody_frames(h_txt, codes, du["d"], du["dur"], T40, du)
 
-    def predict_durations(self, h_txt: Act, codes: torch.Tensor, durations=None) -> dict:
-        """a5-a6: DurationEncoder + duration LSTM + head -> dict(dur int32 [B, T], dsum, logits, d) (device)."""
-        d, ov = self.duration_encoder(h_txt, codes, durations)
-        return self.duration_head(d, ov)
+    def predict_durations(self, h_txt: Act, codes: torch.Tensor, durations=None, text_lens=None) -> dict:
+        """a5-a6: DurationEncoder + duration LSTM + head -> dict(dur int32 [B, T], dsum, logits, d) (device).
+        text_lens (ragged batch): dur[b, :text_lens[b]] and d[b, :text_lens[b]] are those of row b alone at
+        T = text_lens[b]; dur is 0 past it (forced or not), d / logits / dsum rows past it are unspecified, finite."""
+        text_lens = self.text_lens(text_lens, h_txt.B, h_txt.T)
+        d, ov = self.duration_encoder(h_txt, codes, durations, text_lens)
+        return self.duration_head(d, ov, text_lens=text_lens)
 
-    def duration_encoder(self, h_txt: Act, codes: torch.Tensor, durations=None):
+    def _mask_durations(self, ov: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """given durations with those of the padding tokens (t >= lens[b]) zeroed, in the engine's own buffer
+        (device ops, stream-ordered; the caller's tensor is left as it is)"""
+        out = self.buf("pr.dur_ovm", tuple(ov.shape), torch.int32)
+        keep = torch.arange(ov.shape[1], device=ov.device, dtype=torch.int32)[None] < lens[:, None]
+        torch.mul(ov, keep, out=out)
+        return out
+
+    def duration_encoder(self, h_txt: Act, codes: torch.Tensor, durations=None, text_lens=None):
         """a5: DurationEncoder (LSTM + AdaLN layers) -> (d [B, T, pr_in], the given durations as an int32 device
         tensor -- the caller's own when it is one (contiguous [B, T]: read in place, stream-ordered), else the copy
-        pr.dur_ov -- or None)."""
+        pr.dur_ov -- or None).  text_lens (ragged batch): the style is resampled to each row's own length and the
+        BiLSTMs reset at its end; what the AdaLN layers leave in the padding rows is never read by a kept row."""
         S, W = self.spec, self.W
         B, T = h_txt.B, h_txt.T
+        lens = self.text_lens(text_lens, B, T)
         pin = S.pr_in
         xin = self.act("pr.xin", B, T, pin, self.adt)
         assert h_txt.t.dtype == self.adt
@@ -1235,6 +1328,7 @@ class StyleTTSZS:
             h_txt.bs, xin.ld, xin.bs
         a.B, a.L, a.T, a.c0, a.Cs, a.Ch, a.yc0 = B, S.L_s, T, S.style_ac, S.style_pr, S.d_txt, S.d_txt
         a.f32 = int(self.adt == torch.float32)
+        a.lens = lens.data_ptr() if lens is not None else None
         self._call(self.lib.stzs_predictor_prep, a, "pr_prep")
         hout = self.act("pr.hout", B, T, S.pr_hid, self.adt)
         nl = S.pr_layers
@@ -1248,7 +1342,7 @@ class StyleTTSZS:
             gb = self.act("pr.gb", B, T, 2 * S.pr_hid, torch.float32)
             g_at, gs = (lambda i: gb.ptr), 2 * S.pr_hid
         for i in range(nl):
-            self.lstm(W.pr_de[i], xin, hout, f"pr.de{i}")
+            self.lstm(W.pr_de[i], xin, hout, f"pr.de{i}", lens=lens)
             if gs == 2 * S.pr_hid:
                 self.conv(W.pr_aln[i], xin.sl(S.d_txt, S.style_pr), gb, what=f"pr.aln{i}")
             self.rowln(hout, Act(xin.t, 0, S.pr_hid), G=g_at(i), gs=gs, Bt=g_at(i) + S.pr_hid * 4,
@@ -1266,15 +1360,17 @@ class StyleTTSZS:
                     ov.copy_(durations)
         return xin, ov
 
-    def duration_head(self, d: Act, ov=None, hd: Act = None) -> dict:
+    def duration_head(self, d: Act, ov=None, hd: Act = None, text_lens=None) -> dict:
         """a6: duration LSTM + projection + durations kernel (sum of the bin sigmoids, rounded, >= 1; the given
         durations `ov` override it); hd: the duration LSTM's output when already run (lstm_pair)
-        -> dict(dur int32 [B, T], dsum, logits, d)."""
+        -> dict(dur int32 [B, T], dsum, logits, d).  text_lens: the LSTM resets at each row's end, dur and dsum
+        are 0 past it."""
         S, W = self.spec, self.W
         B, T = d.B, d.T
+        lens = self.text_lens(text_lens, B, T)
         if hd is None:
             hd = self.act("pr.hd", B, T, S.pr_hid, self.adt)
-            self.lstm(W.pr_dur_lstm, d, hd, "pr.dur_lstm")
+            self.lstm(W.pr_dur_lstm, d, hd, "pr.dur_lstm", lens=lens)
         logits = self.act("pr.logits", B, T, S.dur_bins, torch.float32)
         self.conv(W.pr_dur_proj, hd, Act(logits.t, 0, S.dur_bins), what="pr.dur_proj")
         dur = self.buf("pr.dur", (B, T), torch.int32)
@@ -1283,13 +1379,15 @@ class StyleTTSZS:
         a.logits, a.override_dur, a.dur, a.dsum = logits.ptr, (ov.data_ptr() if ov is not None else None), \
             dur.data_ptr(), dsum.data_ptr()
         a.ldl, a.bsl, a.B, a.T, a.nbins = logits.ld, logits.bs, B, T, S.dur_bins
+        a.lens = lens.data_ptr() if lens is not None else None
         self._call(self.lib.stzs_durations, a, "durations")
         return dict(dur=dur, dsum=dsum, logits=logits, d=d)
 
     def prosody_frames(self, h_txt: Act, codes: torch.Tensor, d: Act, dur: torch.Tensor, T40: int,
-                       extra: dict = None, pair_dur=False) -> dict:
+                       extra: dict = None, pair_dur=False, text_lens=None) -> dict:
         """a7-a8 for a batch sharing T40 aligned frames: alignment, gathers, shared LSTM, F0 / N curves.
-        pair_dur: the duration LSTM over d runs in the shared LSTM's launch (its output as "_hd")."""
+        pair_dur: the duration LSTM over d runs in the shared LSTM's launch (its output as "_hd"), with the rows'
+        text_lens when the text is ragged (the frames are not: one T40)."""
         S, W = self.spec, self.W
         B, T = h_txt.B, h_txt.T
         pin = S.pr_in
@@ -1308,7 +1406,8 @@ class StyleTTSZS:
         else:
             self.gather(h_txt, idx, enc_in, S.d_txt)
         hd = self.act("pr.hd", B, T, S.pr_hid, self.adt) if pair_dur else None
-        F0, Nn = self.f0n_predictor(en, codes, dur_rec=(W.pr_dur_lstm, d, hd, "pr.dur_lstm") if pair_dur else None)
+        F0, Nn = self.f0n_predictor(en, codes,
+                                    dur_rec=(W.pr_dur_lstm, d, hd, "pr.dur_lstm", text_lens) if pair_dur else None)
         out = dict(extra or {}, dur=dur, idx=idx, T40=T40, en=en, asr_buf=enc_in, d=d, F0=F0, N=Nn)
         if pair_dur:
             out["_hd"] = hd
@@ -1322,7 +1421,7 @@ class StyleTTSZS:
         xs = self.act("pr.xs", B, T40, S.pr_hid, self.adt)
         if dur_rec is None:
             self.lstm(W.pr_shared, en, xs, "pr.shared")
-        else:  # dur_rec = (lw, x, y, key): the duration LSTM beside it, one launch
+        else:  # dur_rec = (lw, x, y, key, text_lens | None): the duration LSTM beside it, one launch
             self.lstm_pair((W.pr_shared, en, xs, "pr.shared"), dur_rec)
         sg = self.mean_rows(codes, S.style_ac, S.style_pr, "pr.sg")
         ng = W.pr_norm
@@ -1863,10 +1962,11 @@ class StyleTTSZS:
         t.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         return t
 
-    def encode_inputs(self, tokens, ref_wav, prompt_idx=None):
+    def encode_inputs(self, tokens, ref_wav, prompt_idx=None, text_lens=None):
         """text encoder || prompt encoder (independent; forked when branch_streams) -> (h_txt, prompt codes)."""
         ref = None if ref_wav is None else ref_wav.to(self.device)
-        return self.fork("enc", lambda: self.text_encode(tokens), lambda: self.prompt_encode(ref, prompt_idx))
+        return self.fork("enc", lambda: self.text_encode(tokens, text_lens),
+                         lambda: self.prompt_encode(ref, prompt_idx))
 
     def capture(self, fn):
         """Capture `fn()` into one HIP graph.  fn must be replay-safe: device-resident inputs, cached
@@ -1892,22 +1992,26 @@ class StyleTTSZS:
         return torch.cuda.is_current_stream_capturing()
 
     def synth(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None, codes=None,
-              n_frames=None, prompt_idx=None, check=True):
+              n_frames=None, prompt_idx=None, check=True, text_lens=None):
         """tokens int [B, T_txt]; ref_wav fp32 [B|1, N]; noise fp32 [B, L_s, code]; durations int [B, T_txt]
         (host tensor, or device tensor + n_frames: no device sync); seeds: per-utterance source-noise
         seeds; prompt_idx: teacher-forced discrete prompt codes [B|1, L_s, G] (ref_wav then unused).
+        text_lens: int [B] (host: range-checked; int32 device tensor: trusted, no sync), each in [1, T_txt] -- a
+        ragged batch: row b is computed as alone on its first text_lens[b] tokens (DESIGN.md "Ragged text
+        batches").  The decoder is not ragged: the rows must still share one frame count.
         check: raise RuntimeError if an LSTM exchange of this call timed out (its durations / prosody would be
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
         -> dict(wav=[B, 600*T40], prompt_idx=[B|1, L_s, G], status=int32 [1], ...)"""
         h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                                   n_frames, prompt_idx)
+                                                   n_frames, prompt_idx, text_lens)
         wav = self.decode(pro, codes, seeds)
         if check and not self._capturing():
             self.check_status()
         return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
 
-    def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx):
+    def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx,
+               text_lens=None):
         """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
         encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
         -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
@@ -1915,18 +2019,20 @@ class StyleTTSZS:
         dev = self.device
         tokens = tokens.to(dev, torch.int32) if tokens.device != dev or tokens.dtype != torch.int32 else tokens
         B = tokens.shape[0]
-        h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx)
+        text_lens = self.text_lens(text_lens, B, tokens.shape[1])  # (host lengths: checked and uploaded once)
+        h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx, text_lens)
         if prompt.shape[0] == 1 and B > 1:
             pe = self.buf("prompt.bc", (B, S.L_s, S.code_dim), torch.float32)
             pe.copy_(prompt.expand(B, -1, -1))
             prompt = pe
         if codes is None:
-            codes = self.sample_style(h, prompt, noise.to(dev, torch.float32), steps, cfg_scale)
-        pro = self.predict_prosody(h, codes, durations, n_frames)
+            codes = self.sample_style(h, prompt, noise.to(dev, torch.float32), steps, cfg_scale, text_lens)
+        pro = self.predict_prosody(h, codes, durations, n_frames, text_lens)
         return h, prompt, codes, pro, list(range(B)) if seeds is None else seeds
 
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
-                     codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None):
+                     codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None,
+                     text_lens=None):
         """configs[4] long-form synthesis with the streaming iSTFT decoder: the text,
         style, prosody and conv stack run over the whole target (AdaIN instance statistics are
         utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
@@ -1936,7 +2042,7 @@ class StyleTTSZS:
         the first chunk is ready after the front and one window's decode."""
         S = self.spec
         _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                              n_frames, prompt_idx)
+                                              n_frames, prompt_idx, text_lens)
         if chunked_halo is not None:  # the chunked decoder: chunk-local statistics, first audio after one window
             yield from self.decode_chunked(pro, codes, seeds, max(1, int(round(chunk_s * S.sr / S.frame40))),
                                            int(chunked_halo))

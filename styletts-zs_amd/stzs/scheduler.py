@@ -15,9 +15,16 @@ Every row is computed exactly as it would be alone (tests/test_gpu_scheduler.py 
 per-request synth() calls), so bucketing is a pure scheduling decision.  Regrouping copies a few small
 per-utterance tensors (text rows, duration-encoder rows, codes) with torch indexing on the device: data
 movement only, no compute.
+
+ragged_text=True (off by default) drops the token count from the phase-1 key: requests sharing a reference length
+run phase 1 as ONE batch padded to its longest text, each row with its own length (the engine's text_lens: row b is
+computed as alone on its first text_lens[b] tokens, DESIGN.md "Ragged text batches"), and the per-utterance rows
+are cut back to their own length before phase 2.  Mixed-length traffic then takes one phase-1 pass per reference
+length instead of one per (token count, reference length).
 """
 from __future__ import annotations
 
+import time
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import List, Optional
@@ -37,39 +44,69 @@ class Request:
 
 
 class BucketScheduler:
-    def __init__(self, engine: StyleTTSZS, max_batch: int = 64, steps: int = 2, cfg_scale: float = 5.0):
+    def __init__(self, engine: StyleTTSZS, max_batch: int = 64, steps: int = 2, cfg_scale: float = 5.0,
+                 ragged_text: bool = False):
         self.eng, self.max_batch, self.steps, self.cfg = engine, max_batch, steps, cfg_scale
+        self.ragged_text = ragged_text
         self.stats = {}
 
     def _chunks(self, ids):
         for i in range(0, len(ids), self.max_batch):
             yield ids[i:i + self.max_batch]
 
+    def phase1_groups(self, reqs: List[Request]):
+        """the phase-1 batches of reqs, in launch order -> [(forced durations?, [request indices])], each of at most
+        max_batch requests that share (token count, reference length, forced) -- or, with ragged_text, only
+        (reference length, forced).  Pure host bookkeeping (reads shapes only)."""
+        g1 = OrderedDict()
+        for i, r in enumerate(reqs):
+            key = (int(r.ref_wav.shape[0]), r.durations is not None)
+            if not self.ragged_text:
+                key = (int(r.tokens.shape[0]),) + key
+            g1.setdefault(key, []).append(i)
+        return [(key[-1], ch) for key, ids in g1.items() for ch in self._chunks(ids)]
+
     def synth(self, reqs: List[Request]) -> List[torch.Tensor]:
         """-> one fp32 waveform [600 * T40_i] per request, in request order (device tensors)."""
         eng, S, dev = self.eng, self.eng.spec, self.eng.device
-        # ---- phase 1: text / prompt / style / durations, grouped by (T_txt, N_ref) ----
-        g1 = OrderedDict()
-        for i, r in enumerate(reqs):
-            g1.setdefault((int(r.tokens.shape[0]), int(r.ref_wav.shape[0]), r.durations is not None), []).append(i)
+        # ---- phase 1: text / prompt / style / durations, grouped by (T_txt, N_ref) -- ragged_text: by N_ref ----
         per = [None] * len(reqs)
         n1 = 0
-        for (_, _, forced), ids in g1.items():
-            for ch in self._chunks(ids):
-                n1 += 1
+        t1 = time.perf_counter()  # (every phase-1 batch ends in a host sync: the wall time is the phase's)
+        for forced, ch in self.phase1_groups(reqs):
+            n1 += 1
+            tl = [int(reqs[i].tokens.shape[0]) for i in ch]
+            Tm = max(tl)
+            lens = None
+            if self.ragged_text and min(tl) < Tm:
+                # pad to the chunk's longest text (any valid symbol: the padding is never read; durations 0) and
+                # hand the rows' own lengths to the engine: checked on the host and uploaded once
+                pad = lambda v: torch.nn.functional.pad(v, (0, Tm - v.shape[0]))
+                tok = torch.stack([pad(reqs[i].tokens) for i in ch]).to(dev, torch.int32)
+                dur_ov = torch.stack([pad(reqs[i].durations) for i in ch]) if forced else None
+                lens = eng.text_lens(tl, len(ch), Tm)
+            else:
                 tok = torch.stack([reqs[i].tokens for i in ch]).to(dev, torch.int32)
-                ref = torch.stack([reqs[i].ref_wav for i in ch]).to(dev, torch.float32)
-                eps = torch.stack([reqs[i].noise for i in ch]).to(dev, torch.float32)
+                dur_ov = torch.stack([reqs[i].durations for i in ch]) if forced else None
+            ref = torch.stack([reqs[i].ref_wav for i in ch]).to(dev, torch.float32)
+            eps = torch.stack([reqs[i].noise for i in ch]).to(dev, torch.float32)
+            if lens is None:  # (the uniform path, call for call as before)
                 h = eng.text_encode(tok)
                 prompt = eng.prompt_encode(ref)
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg)
-                dur_ov = torch.stack([reqs[i].durations for i in ch]) if forced else None
                 du = eng.predict_durations(h, codes, dur_ov)
-                tot = du["dur"].to(torch.int64).sum(1).cpu()  # host sync: frame counts decide phase 2
-                eng.check_status()  # a timed-out LSTM exchange would make these durations wrong: raise
-                for j, i in enumerate(ch):
-                    per[i] = dict(h=h.t[j].clone(), d=du["d"].t[j].clone(), dur=du["dur"][j].clone(),
-                                  codes=codes[j].clone(), T40=int(tot[j]), seed=reqs[i].seed)
+            else:
+                h = eng.text_encode(tok, lens)
+                prompt = eng.prompt_encode(ref)
+                codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg, lens)
+                du = eng.predict_durations(h, codes, dur_ov, lens)
+            tot = du["dur"].to(torch.int64).sum(1).cpu()  # host sync: frame counts decide phase 2
+            eng.check_status()  # a timed-out LSTM exchange would make these durations wrong: raise
+            for j, i in enumerate(ch):
+                T = tl[j]  # the row's own text: what lies past it in a ragged batch is padding
+                per[i] = dict(h=h.t[j, :T].clone(), d=du["d"].t[j, :T].clone(), dur=du["dur"][j, :T].clone(),
+                              codes=codes[j].clone(), T40=int(tot[j]), seed=reqs[i].seed)
+        t1 = time.perf_counter() - t1
         # ---- phase 2: prosody + decoder, grouped by aligned frame count ----
         g2 = OrderedDict()
         for i, p in enumerate(per):
@@ -94,5 +131,5 @@ class BucketScheduler:
                     out[i] = wav[j].clone()
         eng.check_status()  # the phase-2 prosody LSTMs
         self.stats = dict(requests=len(reqs), phase1_batches=n1, phase2_batches=n2,
-                          frame_buckets=sorted(g2.keys()))
+                          frame_buckets=sorted(g2.keys()), phase1_ms=1e3 * t1)
         return out
