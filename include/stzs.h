@@ -52,6 +52,15 @@ int stzs_version(void);
  * Weights are pre-packed bf16 [ks][co_pad][ci_pad] (stzs/weights.py).  ups > 0 selects the
  * polyphase ConvTranspose1d form (ks = 2, pad = 1, co = ups * Co): output row q, phase p lands at
  * t = q*ups + p - ups_pad (+refl, with row 1 mirrored to row 0 for ReflectionPad(1,0)).
+ * Padding columns must be finite: x rows are read in 16-byte vectors, so the columns
+ * [Ci, ceil8(Ci)) of every row x[b, t < T_in] are loaded and meet zero prologue constants and zero
+ * weights (0 * finite = 0; a NaN or Inf there would reach the output).  Nothing else influences the
+ * result: not the rest of a wider row (ldx > ceil8(Ci)), not rows past T_in (bsx > T_in * ldx), and
+ * of pro_mean / pro_rstd / pro_gb only the Ci entries per utterance at stat_bs / gb_bs /
+ * gb_beta_off.  Nothing outside y[b, 0..T_out), [0, Co) is written (STZS_CONV_W_NARROW32 alone
+ * stores whole 8-column vectors: zeros in [Co, ceil8(Co)), which ldy must cover).
+ * tests/test_gpu_conv_probe.py holds every conv form to this on finite-poisoned, over-allocated
+ * operands: same output bits as on compact zero-padded ones, output guards intact.
  * Replaces: the decoder/predictor convs and every denoiser linear (SURVEY §8(a) a2,a9,a11,a12). */
 typedef struct stzs_conv_args {
     const void* x;

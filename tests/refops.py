@@ -164,3 +164,223 @@ def same_bits(a, b):
         return False
     vt = {2: torch.int16, 4: torch.int32}[a.element_size()]
     return torch.equal(a.contiguous().view(vt), b.contiguous().view(vt))
+
+
+# ---- conv family: staged-operand probes and per-element bounds (tests/test_gpu_conv_probe.py, test_refops_conv.py) ----
+# The conv kernels stage pro(x) as bf16 and feed it to MFMA.  With a one-hot weight (delta_weights), bias 0, no residual,
+# alpha 1, every output is one staged value plus products 0 * finite: the launch reads the staged tensor out bit for bit.
+
+def round_bf16(s):
+    """fp64 -> bf16 with ONE rounding (nearest even on 8 significant bits); torch's double -> bfloat16 rounds to fp32
+    first.  Normal range only (the probes' magnitudes)."""
+    m, e = torch.frexp(s.double())
+    return torch.ldexp(torch.round(m * 256.0), e - 8).to(torch.bfloat16)
+
+
+def adain_consts(mean, rstd, gamma, beta):
+    """-> (sc, sh) fp64 [B, C] of the AdaIN prologue: sc = (1 + gamma) rstd, sh = beta - mean sc"""
+    sc = (1 + gamma.double()) * rstd.double()
+    return sc, beta.double() - mean.double() * sc
+
+
+def pro_ref64(x, sc=None, sh=None, act=None, slope=0.0, alpha=None):
+    """the conv prologue in fp64.  x [B, T, C] (stored values), sc / sh [B, C] | None (1, 0), act None | "leaky" |
+    "snake" (v + sin^2(alpha v) / alpha, alpha [C]) -> (s fp64, its bf16 rounding -- one rounding from fp64 --, the
+    magnitude |x sc| + |sh| (+ 1 / alpha for Snake) that the fp32 prologue's rounding errors scale with)."""
+    x = x.double()
+    v, mag = x, x.abs()
+    if sc is not None:
+        v = x * sc.double()[:, None, :] + sh.double()[:, None, :]
+        mag = (x * sc.double()[:, None, :]).abs() + sh.double().abs()[:, None, :]
+    if act == "leaky":
+        s = torch.where(v >= 0, v, v * slope)
+    elif act == "snake":
+        a = alpha.double()[None, None, :]
+        s = v + torch.sin(a * v) ** 2 / a
+        mag = mag + 1 / a
+    else:
+        assert act is None, act
+        s = v
+    return s, round_bf16(s), mag
+
+
+def staged_check(got, s, sbf, mag):
+    """a staged bf16 tensor against pro_ref64's (s, sbf, mag) -> (the largest |got - s| / (2^-8 |s| + 2^-16 mag), the
+    share of elements whose bits differ from sbf).  The first must be <= 1, the second <= 0.01."""
+    ratio = (got.double() - s).abs() / (s.abs() * 2.0 ** -8 + mag * 2.0 ** -16)
+    diff = got.contiguous().view(torch.int16) != sbf.contiguous().view(torch.int16)
+    return ratio.max().item(), diff.double().mean().item()
+
+
+def conv_terms_ref(xhat, w, b, *, pad=0, dil=1, stride=1, res=None, res_tdiv=1, out_scale=1.0, acc_in=None, beta=0.0,
+                   ups=0, ups_pad=0, refl=0):
+    """conv_ref / convT_ref on already-staged operands, in fp64, with the magnitude its rounding errors scale with.
+    xhat [B, T, Ci] (the staged values), w [Co, Ci, k] (ups > 0: ConvTranspose1d weights [Ci, Co, 2 ups], stride ups,
+    padding ups_pad, ReflectionPad(refl, 0)) as the kernel holds them (bf16-rounded by the caller), b [Co] | None ->
+    (y, terms) [B, T_out, Co] fp64; terms is the same conv on |xhat|, |w|, |b|, plus |res| and |beta acc_in|."""
+    def run(x, ww, bb, r, a):
+        x = x.double().transpose(1, 2)
+        bb = bb.double() if bb is not None else None
+        if ups:
+            y = F.conv_transpose1d(x, ww.double(), bb, stride=ups, padding=ups_pad)
+            if refl:
+                y = F.pad(y, (refl, 0), mode="reflect")
+        else:
+            y = F.conv1d(x, ww.double(), bb, stride=stride, padding=pad, dilation=dil)
+        y = y.transpose(1, 2)
+        if r is not None:
+            r = r.double()
+            if res_tdiv > 1:
+                r = r.repeat_interleave(res_tdiv, dim=1)[:, : y.shape[1]]
+            y = y + r
+        y = y * out_scale
+        if a is not None:
+            y = y + beta * a.double()
+        return y
+    ab = lambda t: t.abs() if t is not None else None
+    y = run(xhat, w, b, res, acc_in)
+    out_scale, beta = abs(out_scale), abs(beta)
+    return y, run(xhat.abs(), w.abs(), ab(b), ab(res), ab(acc_in))
+
+
+def dense_ratio(got, ref, terms, K, bf16_out):
+    """the largest |got - ref| / bound, bound = (2^-8 |ref| if the output is bf16) + 2 (K + 4) 2^-24 terms: one output
+    rounding plus K fp32 accumulation steps (and the epilogue's four), the factor 2 for accumulation that is not
+    round-to-nearest inside an MFMA block.  Must be <= 1."""
+    bound = 2.0 * (K + 4) * 2.0 ** -24 * terms
+    if bf16_out:
+        bound = bound + ref.abs() * 2.0 ** -8
+    return ((got.double() - ref).abs() / bound.clamp_min(1e-300)).max().item()
+
+
+def delta_weights(Co, Ci, k, j0, m=0):
+    """one-hot conv weight [Co, Ci, k]: w[co, ci, j] = 1 where ci == co + m Co and j == j0 -- output channel co reads
+    out staged channel co + m Co at tap j0 (exactly 0 where co + m Co >= Ci)"""
+    w = torch.zeros(Co, Ci, k)
+    n = min(Co, Ci - m * Co)
+    if n > 0:
+        i = torch.arange(n)
+        w[i, i + m * Co, j0] = 1.0
+    return w
+
+
+def delta_weights_T(Ci, Co, k, j0, m=0):
+    """the ConvTranspose1d twin [Ci, Co, k]: w[ci, co, j] = 1 where ci == co + m Co and j == j0"""
+    return delta_weights(Co, Ci, k, j0, m).transpose(0, 1).contiguous()
+
+
+def fill_bits(shape, dtype, fill, device="cpu"):
+    """a tensor of `dtype` filled with `fill`: a float value, or an int bit pattern (e.g. a NaN payload)"""
+    if isinstance(fill, int):
+        it = {2: torch.int16, 4: torch.int32}[torch.empty(0, dtype=dtype).element_size()]
+        bits = fill - (1 << (8 * it.itemsize)) if fill >= 1 << (8 * it.itemsize - 1) else fill
+        return torch.full(shape, bits, dtype=it, device=device).view(dtype)
+    return torch.full(shape, fill, dtype=dtype, device=device)
+
+
+def guarded(shape_logical, pads, fill, dtype=torch.bfloat16, device="cpu"):
+    """an over-allocated buffer around a logical [B, T, C] tensor.  pads = (extra rows per utterance, channel offset
+    c0, extra columns behind ceil8(C)); every element starts as `fill` (fill_bits) -> (buf [B, T + rows, c0 + ceil8(C) +
+    cols], the engine Act over buf[:, :T] at channels [c0, c0 + C): its batch stride is the buffer's)."""
+    from stzs.engine import Act
+    B, T, Cc = shape_logical
+    rows, c0, cols = pads
+    buf = fill_bits((B, T + rows, c0 + (Cc + 7) // 8 * 8 + cols), dtype, fill, device)
+    return buf, Act(buf[:, :T], c0, Cc)
+
+
+def guards_intact(buf, view, fill, C=None):
+    """everything of buf (from guarded, with the same `fill`) outside view's [B, T, C] still holds the fill, bit for
+    bit.  C: the written width where it differs from view.C (a form that stores whole 8-column vectors)."""
+    C = view.C if C is None else C
+    probe = buf.clone()
+    fill = fill_bits(buf.shape, buf.dtype, fill, buf.device)
+    probe[:, :view.T, view.c0:view.c0 + C] = fill[:, :view.T, view.c0:view.c0 + C]
+    return same_bits(probe, fill)
+
+
+def _bits(t):
+    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def _first(mask):
+    """the first True index of a mask, as a tuple (for a failure message)"""
+    return tuple(int(v) for v in mask.nonzero()[0])
+
+
+def probe_readout(run, *, T, Ci, Co, k, dil=1, pad=0, stride=1, tile=64):
+    """read a conv's staged operand out through delta weights.  run(j0, m) launches the conv with delta_weights(Co, Ci,
+    k, j0, m), bias 0, no residual, alpha 1 and returns y [B, T_out, Co]: y[b, t, co] must be the staged value
+    S[b, t stride + j0 dil - pad, co + m Co], or exactly +0 in the zero padding and where co + m Co >= Ci.
+    -> (S [B, T, Ci] in y's dtype, problems): problems lists, with (tap, utterance, row, tile row, channel), every tap
+    whose padding is not +0 or whose rows differ in bits from the same rows read through an earlier tap, and the rows
+    no tap reached."""
+    nb = (Ci + Co - 1) // Co
+    S, filled, problems = None, None, []
+    for j0 in range(k):
+        y = torch.cat([run(j0, m) for m in range(nb)], -1)
+        dev = y.device
+        if S is None:
+            S = torch.zeros(y.shape[0], T, Ci, dtype=y.dtype, device=dev)
+            filled = torch.zeros(T, dtype=torch.bool, device=dev)
+        bad = _bits(y[:, :, Ci:]) != 0
+        if bad.any():
+            b, t, c = _first(bad)
+            problems.append(f"tap {j0}: channel {Ci + c} >= Ci not +0 at utterance {b} row {t} (row {t % tile} of tile {t // tile})")
+        y = y[:, :, :Ci]
+        r = torch.arange(y.shape[1], device=dev) * stride + j0 * dil - pad
+        ok = (r >= 0) & (r < T)
+        bad = _bits(y[:, ~ok]) != 0
+        if bad.any():
+            b, i, c = _first(bad)
+            t = int((~ok).nonzero()[i])
+            problems.append(f"tap {j0}: zero padding not +0 at utterance {b} output row {t} (row {t % tile} of tile "
+                            f"{t // tile}) channel {c}")
+        rows, vals = r[ok], y[:, ok]
+        seen = filled[rows]
+        if seen.any():
+            bad = _bits(vals[:, seen]) != _bits(S[:, rows[seen]])
+            if bad.any():
+                b, i, c = _first(bad)
+                t = int(ok.nonzero()[seen.nonzero()[i]])
+                problems.append(f"tap {j0}: staged row {int(rows[seen][i])} read at output row {t} (row {t % tile} of "
+                                f"tile {t // tile}) channel {c} utterance {b} differs from an earlier tap's read")
+        S[:, rows[~seen]] = vals[:, ~seen]
+        filled[rows] = True
+    if not bool(filled.all()):
+        problems.append(f"staged rows never read: {filled.logical_not().nonzero().flatten().tolist()[:8]}")
+    return S, problems
+
+
+def polyphase_expect(S, j0, *, ups, ups_pad, refl):
+    """the polyphase ConvTranspose's exact output for delta_weights_T(.., j0) on staged rows S [B, T, C]: row q lands at
+    t = q ups + j0 - ups_pad when that is in [0, T ups), shifted by refl, and row 0 mirrors row 2 (ReflectionPad(1, 0));
+    every other row is +0 -> [B, T ups + refl, C]"""
+    B, T, Cc = S.shape
+    E = torch.zeros(B, T * ups + refl, Cc, dtype=S.dtype, device=S.device)
+    t = torch.arange(T, device=S.device) * ups + j0 - ups_pad
+    ok = (t >= 0) & (t < T * ups)
+    E[:, t[ok] + refl] = S[:, ok]
+    if refl:
+        E[:, 0] = E[:, 2]
+    return E
+
+
+def probe_readout_T(run, *, T, Ci, Co, ups, ups_pad, refl):
+    """probe_readout for the polyphase ConvTranspose (k = 2 ups): run(j0, m) uses delta_weights_T(Ci, Co, 2 ups, j0, m)
+    and returns y [B, T ups + refl, Co].  S is read through tap j0 = ups_pad (row q at t = q ups, every q in range);
+    every tap's whole output must then equal polyphase_expect(S, j0) bit for bit -> (S [B, T, Ci], problems)."""
+    nb = (Ci + Co - 1) // Co
+    ys = {j0: torch.cat([run(j0, m) for m in range(nb)], -1) for j0 in range(2 * ups)}
+    S = ys[ups_pad][:, refl:T * ups + refl:ups, :Ci].contiguous()
+    problems = []
+    for j0, y in ys.items():
+        E = polyphase_expect(S, j0, ups=ups, ups_pad=ups_pad, refl=refl)
+        bad = _bits(y[:, :, :Ci]) != _bits(E)
+        if bad.any():
+            b, t, c = _first(bad)
+            problems.append(f"tap {j0} (phase {j0 % ups}): utterance {b} output row {t} channel {c} is "
+                            f"{float(y[b, t, c])}, expected {float(E[b, t, c])}")
+        if bool((_bits(y[:, :, Ci:]) != 0).any()):
+            problems.append(f"tap {j0}: channels >= Ci not +0")
+    return S, problems
