@@ -396,7 +396,9 @@ typedef struct stzs_dur_args {
 int stzs_durations(const stzs_dur_args* a, void* stream);
 
 /* alignment: exclusive scan of dur -> token index per aligned frame idx[b, f], f < T40;
- * frames beyond sum(dur) get -1; total[b] = sum(dur). */
+ * frames beyond sum(dur) get -1; total[b] = sum(dur).  Durations may be 0 anywhere in a row (such a token owns
+ * no frame) and the rows' totals may differ.  T <= 16384 (one workgroup per utterance holds the T + 1 scan entries
+ * in LDS: 65 540 bytes at the limit); a larger T returns STZS_ESHAPE and launches nothing. */
 typedef struct stzs_align_args {
     const int32_t* dur;
     int32_t* idx;
@@ -447,7 +449,11 @@ int stzs_f0n_down(const stzs_f0n_args* a, void* stream);
 /* ---- decoder source + iSTFT ---- */
 /* harmonic source (SineGen, counter-RNG noise, Linear(9->1)+tanh) and its n_fft STFT
  * (real | imag) -> har [B, Tf, ldh] bf16, Tf = T80*hop/hop_s + 1.  `prefix` is caller workspace
- * [B][nh][T80] f32 (frame-rate phase prefix, computed in fp64 and wrapped every frame). */
+ * [B][nh][T80] f32 (frame-rate phase prefix, computed in fp64 and wrapped every frame).
+ * Accepted: nh <= 64, n_fft <= 64, ldh >= 2 * (n_fft/2 + 1), and (hop_s * 255 + n_fft - 2) / hop + 2 <= 8 (the
+ * 80-fps frames that the samples of one workgroup's 256 STFT frames can span: hop >= 185 at n_fft 20 / hop_s 5).
+ * Every check precedes the first launch: a call that returns an error has run nothing and left `prefix` and `har`
+ * untouched. */
 typedef struct stzs_source_args {
     const float* f0;
     const uint32_t* seeds;
@@ -462,7 +468,11 @@ typedef struct stzs_source_args {
 int stzs_harmonic_source(const stzs_source_args* a, void* stream);
 
 /* iSTFT: post [B, Tf, ldp] f32 (n_bins log-mag | n_bins phase-arg) -> wav [B, (Tf-1)*hop_s]
- * spec = exp(m) * exp(i sin(p)); hann window, center=True, window-square normalisation */
+ * spec = exp(m) * exp(i sin(p)); hann window, center=True, window-square normalisation.
+ * Accepted geometries (stzs_istft and stzs_istft_stream): n_fft is 16 or 20, 1 <= hop_s < n_fft, Tf >= 2.
+ * hop_s == n_fft is refused (STZS_ESHAPE): the periodic Hann window's first tap is 0, so the samples f * n_fft would
+ * have a zero envelope (torch.istft refuses it too).  The phase argument p is reduced with a two-constant 2 pi that is
+ * exact for |p| < 2^17. */
 typedef struct stzs_istft_args {
     const float* post;
     float* wav;
@@ -488,7 +498,8 @@ typedef struct stzs_istft_stream_args {
     int32_t B, f0, Fc, final_chunk, n_fft, hop_s;
 } stzs_istft_stream_args;
 int stzs_istft_stream(const stzs_istft_stream_args* a, void* stream);
-/* -> halo (>= 0) or a negative error; [*n0, *n1) = output samples of the chunk */
+/* -> halo (>= 0) or a negative error; [*n0, *n1) = output samples of the chunk.  Host arithmetic only: any even
+ * n_fft <= 64 with 1 <= hop_s < n_fft (hop_s == n_fft: STZS_ESHAPE, as the launches). */
 int stzs_istft_stream_span(int f0, int Fc, int final_chunk, int n_fft, int hop_s, int64_t* n0, int64_t* n1);
 
 /* ---- reference-prompt front end (csrc/frontend.hip) -------------------------

@@ -14,8 +14,10 @@
 // Work split: one workgroup per 256 - halo frames of the chunk, so the 256 frame signals overlapping its output span
 // (its own + the halo) are synthesised once into LDS by the 256 threads in ONE pass (256 own frames + 3 halo took a
 // second pass for 3 threads, i.e. the whole workgroup twice as long), then each thread overlap-adds its output
-// samples.  Spectrum from the hardware transcendentals (v_exp / v_sin / v_cos, ~1e-6 relative; the libm forms' range
-// reduction was most of the frame synthesis).  HBM-bound: reads n_fft + 2 floats per frame, writes hop_s samples.
+// samples.  Spectrum from the hardware transcendentals (v_exp / v_sin / v_cos, ~1e-6 relative each; the libm forms' range
+// reduction was most of the frame synthesis): every sample within 0.09 of (3e-6 + (nb + halo + 6) 2^-24) x the sum of
+// its bins' magnitudes, edge samples and phase arguments up to +-2^17 included (MI355X, tests/test_gpu_backend.py).
+// HBM-bound: reads n_fft + 2 floats per frame, writes hop_s samples.
 #include "common.hpp"
 
 namespace {
@@ -155,13 +157,17 @@ int launch(const IstftJob& j, int nfft, int B, long m_lo, hipStream_t s) {
     return STZS_OK;
 }
 
-bool bad_geom(int nfft, int hs) { return nfft <= 0 || nfft > 64 || nfft % 2 || hs <= 0 || hs > nfft; }
+// hop_s == n_fft is refused: the padded samples f * n_fft would be covered by the zero tap win[0] alone (envelope 0,
+// the sample 0 / 0); torch.istft refuses that geometry as well (its non-zero overlap-add condition)
+bool bad_geom(int nfft, int hs) { return nfft <= 0 || nfft > 64 || nfft % 2 || hs <= 0 || hs >= nfft; }
+bool bad_size(int nfft) { return nfft != 16 && nfft != 20; }  // the instantiated transform sizes
 
 }  // namespace
 
 extern "C" int stzs_istft(const stzs_istft_args* a, void* stream) {
     if (!a || !a->post || !a->wav) return STZS_EINVAL;
-    if (a->B <= 0 || a->Tf < 2 || bad_geom(a->n_fft, a->hop_s) || a->ldp < a->n_fft + 2) return STZS_ESHAPE;
+    if (a->B <= 0 || a->Tf < 2 || bad_geom(a->n_fft, a->hop_s) || bad_size(a->n_fft) || a->ldp < a->n_fft + 2)
+        return STZS_ESHAPE;
     IstftJob j{};
     j.post = a->post;
     j.wav = a->wav;
@@ -190,7 +196,8 @@ extern "C" int stzs_istft_stream_span(int f0, int Fc, int final_chunk, int n_fft
 
 extern "C" int stzs_istft_stream(const stzs_istft_stream_args* a, void* stream) {
     if (!a || !a->post || !a->wav) return STZS_EINVAL;
-    if (a->B <= 0 || a->f0 < 0 || a->Fc <= 0 || bad_geom(a->n_fft, a->hop_s) || a->ldp < a->n_fft + 2)
+    if (a->B <= 0 || a->f0 < 0 || a->Fc <= 0 || bad_geom(a->n_fft, a->hop_s) || bad_size(a->n_fft) ||
+        a->ldp < a->n_fft + 2)
         return STZS_ESHAPE;
     if (a->f0 > 0 && !a->tail_in) return STZS_EINVAL;  // frames before the chunk reach its samples
     if ((a->tail_in || a->tail_out) && a->ldt < a->n_fft + 2) return STZS_ESHAPE;

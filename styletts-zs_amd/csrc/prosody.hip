@@ -188,7 +188,14 @@ extern "C" int stzs_durations(const stzs_dur_args* a, void* stream) {
 extern "C" int stzs_alignment(const stzs_align_args* a, void* stream) {
     if (!a || !a->dur || !a->idx || !a->total) return STZS_EINVAL;
     if (a->B <= 0 || a->T <= 0 || a->T40 <= 0 || a->T > 16384) return STZS_ESHAPE;
-    hipLaunchKernelGGL(align_kernel, dim3(a->B), dim3(256), (a->T + 1) * sizeof(int),
+    // T + 1 scan entries in dynamic LDS: 65 540 bytes at T = 16384.  The runtime's headers do not say whether a request
+    // above 64 KiB needs the function attribute; lstm.hip's exchange kernels set it and run, so this launch does the
+    // same (T = 16384 is tested against the reference).  A refused attribute is an error, never a launch.
+    const size_t lds = (size_t)(a->T + 1) * sizeof(int);
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return STZS_EHIP;
+    hipLaunchKernelGGL(align_kernel, dim3(a->B), dim3(256), lds,
                        reinterpret_cast<hipStream_t>(stream), *a);
     STZS_LAUNCH_CHECK();
     return STZS_OK;

@@ -4,12 +4,16 @@
 // Phase accuracy (SURVEY §7 "SineGen phase cumsum drifts in fp32"): a per-(utterance, harmonic)
 // thread accumulates the frame-rate phase prefix in fp64 and wraps it every 80-fps frame; the
 // in-frame phase is then prefix + (j+1) * f/sr in fp32 (|arg| < 60 cycles, so < 4e-6 cycles of
-// error).  Every fp32/fp64 op that must agree bit-for-bit with the oracle uses explicit _rn
-// intrinsics (no FMA contraction).  Samples are generated once per workgroup into LDS
+// error).  Every fp32/fp64 op that must agree bit-for-bit with the oracle is a single IEEE operation whose
+// neighbours cannot be fused into it: the _rn intrinsics are the plain operators, so a product that feeds a sum goes
+// through add_mul_2r (the product held in a register the compiler cannot fuse through) or through memory.
+// Samples are generated once per workgroup into LDS
 // (reflect-padded at the ends, centre=True) and consumed by all frames that overlap them; the
 // per-frame phase increments and prefixes of the few frames a workgroup spans sit in LDS.  Sine and
 // the noise's Box-Muller use the hardware transcendentals (v_sin / v_cos in revolutions, v_log):
-// the counter stream is the oracle's, the transform within ~1e-6 of its fp64 one.
+// the counter stream is the oracle's, the transform within ~1e-6 of its fp64 one (measured on MI355X per sample
+// through the inverse transform of the fp32 bins, tests/test_gpu_backend.py: the sine within 1.9e-7 below one cycle
+// of phase, every fp32 bin within 0.17 of the bound that 1e-6 for the sine and 2e-6 for Box-Muller give).
 #include "common.hpp"
 
 namespace {
@@ -33,7 +37,8 @@ STZS_DEV float counter_normal(uint32_t key, uint32_t idx) {
     return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
 }
 // the same counter pair as counter_normal, Box-Muller in fp32 hardware intrinsics (v_log_f32,
-// v_sqrt_f32, v_cos_f32 in revolutions): within ~2e-6 of the fp64 transform (tests/test_gpu_ops.py).
+// v_sqrt_f32, v_cos_f32 in revolutions): within ~2e-6 of the fp64 transform (1.3e-6 measured on MI355X,
+// tests/test_gpu_backend.py).
 // hi0 = hash32(2 idx), hi1 = hash32(2 idx + 1): the counter hashes do not depend on the stream key, so a sample's
 // harmonics share them (the same values as counter_normal computes)
 STZS_DEV float counter_normal_fast(uint32_t key, uint32_t hi0, uint32_t hi1) {
@@ -42,6 +47,16 @@ STZS_DEV float counter_normal_fast(uint32_t key, uint32_t hi0, uint32_t hi1) {
     const float u1 = ((float)(a >> 8) + 1.f) * (1.f / 16777216.f);
     const float u2 = (float)(b >> 8) * (1.f / 16777216.f);
     return __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1)) * __builtin_amdgcn_cosf(u2);
+}
+// a + b * c in two IEEE fp32 roundings, as the oracle computes the in-frame phase.  HIP's __fmul_rn / __fadd_rn are the
+// plain operators, which the build's -ffp-contract=fast fuses into one v_fma (one rounding: the phase then differs from
+// the oracle's by an ulp of t in ~2 % of the samples, 3e-6 of a sine at 400 Hz -- tests/test_gpu_backend.py).  That
+// fusion is the back end's and ignores a contract(off) pragma, so the rounded product passes through an empty asm
+// statement, which the compiler cannot see through.
+STZS_DEV float add_mul_2r(float a, float b, float c) {
+    float p = b * c;
+    asm("" : "+v"(p));
+    return a + p;
 }
 STZS_DEV float initial_phase(uint32_t key) {
     return (float)((double)(hash32(key ^ 0xA5A5A5A5u) >> 8) * (1.0 / 16777216.0));
@@ -141,7 +156,7 @@ __global__ __launch_bounds__(256) void source_stft_kernel(const stzs_source_args
             const uint32_t hi0 = hash32((uint32_t)n * 2u), hi1 = hash32((uint32_t)n * 2u + 1u);
             float acc = 0.f;
             for (int h = 0; h < a.nh; ++h) {
-                const float t = __fadd_rn(fp[h], __fmul_rn(jj, fi[h]));
+                const float t = add_mul_2r(fp[h], jj, fi[h]);
                 const float th = __fsub_rn(t, floorf(t));  // wrapped phase, cycles
                 const float sine = amp * __builtin_amdgcn_sinf(th);
                 const float z = counter_normal_fast(keys[h], hi0, hi1);
@@ -227,14 +242,16 @@ extern "C" int stzs_harmonic_source(const stzs_source_args* a, void* stream) {
         return STZS_ESHAPE;
     if (a->ldh < 2 * (a->n_fft / 2 + 1)) return STZS_ESHAPE;
     if (a->har_dtype != STZS_BF16 && a->har_dtype != STZS_F32) return STZS_EDTYPE;
+    // every shape check before the first launch: a refused call has run nothing (prefix stays untouched)
+    const int NS = a->hop_s * (FB - 1) + a->n_fft;
+    // NS consecutive samples touch at most (NS - 2) / hop + 2 frames of hop samples (first sample last in its frame)
+    if (a->hop <= 0 || (NS - 2) / a->hop + 2 > KW) return STZS_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n = a->B * a->nh;
     hipLaunchKernelGGL(phase_prefix_kernel, dim3(n), dim3(256), 0, s, *a);
     STZS_LAUNCH_CHECK();
     const int N = a->T80 * a->hop;
     const int Tf = N / a->hop_s + 1;
-    const int NS = a->hop_s * (FB - 1) + a->n_fft;
-    if (NS / a->hop + 2 > KW) return STZS_ESHAPE;
     const size_t lds = (size_t)(NS + 3 * a->n_fft) * 4 + (size_t)a->nh * (8 + 4 + 2 * KW * 4);
     if (a->n_fft == 20)
         hipLaunchKernelGGL(source_stft_kernel<20>, dim3((Tf + FB - 1) / FB, a->B), dim3(256), lds, s, *a);

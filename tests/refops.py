@@ -384,3 +384,269 @@ def probe_readout_T(run, *, T, Ci, Co, ups, ups_pad, refl):
         if bool((_bits(y[:, :, Ci:]) != 0).any()):
             problems.append(f"tap {j0}: channels >= Ci not +0")
     return S, problems
+
+
+# ---- waveform back end and integer path (tests/test_gpu_backend.py, test_refops_backend.py) ----
+# Plain parameters throughout (no Spec: Spec.check() admits the shipped geometry only).  numpy, fp64 unless stated.
+
+def phase_prefix_ref(f0, nh, hop, sr):
+    """f0 [B, T80] fp32 -> the per-80-fps-frame phase prefix [B, nh, T80] fp64, wrapped every frame: the recurrence of
+    oracle.frame_phase_prefix (acc = frac(acc + hop * (f0 (h + 1) / sr)), one IEEE fp64 rounding per operation)."""
+    f = np.asarray(f0, np.float32).astype(np.float64)
+    B, T = f.shape
+    inc = f[:, None, :] * np.arange(1, nh + 1, dtype=np.float64)[None, :, None] / np.float64(sr)
+    out = np.zeros((B, nh, T))
+    acc = np.zeros((B, nh))
+    for k in range(T):
+        out[:, :, k] = acc
+        acc = acc + np.float64(hop) * inc[:, :, k]
+        acc = acc - np.floor(acc)
+    return out
+
+
+def source_theta32(f0, seeds, *, hop, nh, sr, first_phase_zero=True, n=None):
+    """the wrapped phase theta [B, nh, len(n)] fp32 (cycles) at the samples n (None: all N = T80 hop) with the fp32 operation sequence of oracle.harmonic_source:
+    fadd(prefix32, ph0), fadd(., fmul(j, finc)), t - floor(t), finc = fdiv(fmul(f0, h + 1), sr) -- one rounding each, no
+    contraction.  The fundamental starts at phase 0 (first_phase_zero; False is a defect the self-checks plant).
+    -> (theta, prefix32 [B, nh, T80], keys [B][nh])"""
+    from oracle.stzs_ref import initial_phase, stream_key
+    f = np.asarray(f0, np.float32)
+    B, T = f.shape
+    n = np.arange(T * hop) if n is None else np.asarray(n)
+    k = n // hop
+    j = (n - k * hop + 1).astype(np.float32)
+    pre = phase_prefix_ref(f, nh, hop, sr).astype(np.float32)
+    theta = np.zeros((B, nh, len(n)), np.float32)
+    keys = []
+    for b in range(B):
+        keys.append([stream_key(int(seeds[b]), h) for h in range(nh)])
+        for h in range(nh):
+            ph0 = np.float32(0.0) if h == 0 and first_phase_zero else initial_phase(keys[b][h])
+            finc = (f[b] * np.float32(h + 1)).astype(np.float32) / np.float32(sr)
+            t = (pre[b, h] + ph0).astype(np.float32)[k]
+            t = (t + (j * finc[k]).astype(np.float32)).astype(np.float32)
+            theta[b, h] = (t - np.floor(t)).astype(np.float32)
+    return theta, pre, keys
+
+
+def _mix32(x):
+    """lowbias32 on 32-bit values carried in uint64 lanes (the counter RNG's hash, restated)"""
+    m = np.uint64(0xFFFFFFFF)
+    x = np.asarray(x, dtype=np.uint64) & m
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & m
+    return x ^ (x >> np.uint64(16))
+
+
+def uniforms24(key, idx):
+    """the two 24-bit uniforms of counter_normal(key, idx): u1 in (0, 1], u2 in [0, 1), exact in fp32 and fp64"""
+    i = np.asarray(idx, dtype=np.uint64)
+    a = _mix32(np.uint64(key) ^ _mix32(i * np.uint64(2)))
+    b = _mix32(np.uint64(key) ^ _mix32(i * np.uint64(2) + np.uint64(1)))
+    return ((a >> np.uint64(8)).astype(np.float64) + 1.0) / 16777216.0, (b >> np.uint64(8)).astype(np.float64) / 16777216.0
+
+
+def reflect_index(p, N, n_fft):
+    """padded sample index p (centre=True) -> signal index, torch's reflect padding: -n on the left, 2 (N - 1) - n on
+    the right"""
+    n = np.asarray(p) - n_fft // 2
+    n = np.where(n < 0, -n, n)
+    return np.where(n >= N, 2 * (N - 1) - n, n)
+
+
+def source_ref(f0, seeds, merge_w, *, hop, n_fft, hop_s, nh, sr, sine_amp, noise_std, voiced_thr, frames=None):
+    """the harmonic source and its STFT.  f0 [B, T80] fp32, seeds [B], merge_w [nh + 1] fp32 (weights, bias).  theta is
+    source_theta32 (the part the kernel shares bit for bit); everything after it is fp64: sine, Box-Muller on the same
+    24-bit uniforms, merge, tanh, reflect padding, periodic Hann, DFT.  frames: the frame indices to transform (None =
+    all Tf = N / hop_s + 1) -> dict(bins [B, len(frames), 2 nb] (real | imag), A1 = sum_i win_i, A2 [B, len(frames)] =
+    sum_i |x_i win_i|, x [B, N] (NaN at the samples no chosen frame reads), prefix32 [B, nh, T80])."""
+    f = np.asarray(f0, np.float32)
+    w = np.asarray(merge_w, np.float32).astype(np.float64)
+    B, T = f.shape
+    N = T * hop
+    Tf = N // hop_s + 1
+    fr = np.arange(Tf) if frames is None else np.asarray(frames)
+    i = np.arange(n_fft)
+    src = reflect_index(fr[:, None] * hop_s + i[None, :], N, n_fft)  # [F, n_fft] signal indices
+    n = np.unique(src)
+    theta, pre, keys = source_theta32(f, seeds, hop=hop, nh=nh, sr=sr, n=n)
+    voiced = (f > np.float32(voiced_thr))[:, n // hop]
+    namp = np.where(voiced, np.float64(np.float32(noise_std)), np.float64(np.float32(sine_amp)) / 3.0)
+    x = np.full((B, N), np.nan)
+    for b in range(B):
+        acc = np.zeros(len(n))
+        for h in range(nh):
+            u1, u2 = uniforms24(keys[b][h], n)
+            z = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * u2)
+            sine = np.float64(np.float32(sine_amp)) * np.sin(2.0 * math.pi * theta[b, h].astype(np.float64))
+            acc = acc + w[h] * (sine * voiced[b] + namp[b] * z)
+        x[b, n] = np.tanh(acc + w[nh])
+    win = 0.5 - 0.5 * np.cos(2.0 * math.pi * i / n_fft)
+    xi = x[:, src] * win  # [B, F, n_fft]
+    nb = n_fft // 2 + 1
+    ang = 2.0 * math.pi * np.outer(i, np.arange(nb)) / n_fft
+    bins = np.concatenate([xi @ np.cos(ang), -(xi @ np.sin(ang))], -1)
+    return dict(bins=bins, A1=float(win.sum()), A2=np.abs(xi).sum(-1), x=x, prefix32=pre)
+
+
+def istft_ref(post, n_fft, hop_s):
+    """post [B, Tf, >= 2 nb] fp32 (log-magnitudes | phase arguments) -> (wav [B, (Tf - 1) hop_s], S the same shape, min
+    env), fp64 from the fp32 inputs: mag = exp(m), ph = sin(p), irfft by the explicit DFT (the imaginary parts of DC
+    and Nyquist do not enter), periodic Hann, overlap-add, window-square envelope, centre trim.  S = sum over a
+    sample's frames and bins of |mag_k| c_k win_i / (n_fft env), c_k = 1 for DC and Nyquist and 2 otherwise: the
+    magnitude its rounding errors scale with.  min env is taken over the emitted samples."""
+    p = np.asarray(post, np.float32).astype(np.float64)
+    B, Tf = p.shape[:2]
+    nb = n_fft // 2 + 1
+    mag, ph = np.exp(p[:, :, :nb]), np.sin(p[:, :, nb:2 * nb])
+    re, im = mag * np.cos(ph), mag * np.sin(ph)
+    i = np.arange(n_fft)
+    ang = 2.0 * math.pi * np.outer(np.arange(nb), i) / n_fft
+    c = np.full(nb, 2.0)
+    c[0] = c[-1] = 1.0
+    win = 0.5 - 0.5 * np.cos(2.0 * math.pi * i / n_fft)
+    fr = ((re * c) @ np.cos(ang) - (im * c) @ np.sin(ang)) / n_fft * win  # [B, Tf, n_fft]
+    fs = ((mag * c).sum(-1, keepdims=True) / n_fft) * win                   # the same sum on magnitudes
+    M = (Tf - 1) * hop_s + n_fft
+    y, s, env = np.zeros((B, M)), np.zeros((B, M)), np.zeros(M)
+    for t in range(n_fft):
+        sl = slice(t, t + Tf * hop_s, hop_s)
+        y[:, sl] += fr[:, :, t]
+        s[:, sl] += fs[:, :, t]
+        env[sl] += win[t] ** 2
+    keep = slice(n_fft // 2, n_fft // 2 + (Tf - 1) * hop_s)
+    env = env[keep]
+    return y[:, keep] / env, s[:, keep] / env, float(env.min())
+
+
+def istft_halo(n_fft, hop_s):
+    """frames before a chunk that still reach its samples: ceil(n_fft / hop_s) - 1"""
+    return -(-n_fft // hop_s) - 1
+
+
+def istft_span_ref(f0, Fc, final, n_fft, hop_s):
+    """the output samples [n0, n1) a streaming chunk of frames [f0, f0 + Fc) emits, from include/stzs.h's wording:
+    every sample whose overlapping frames are all known -- padded sample m (output n = m - n_fft / 2) overlaps frames
+    up to m // hop_s, so m < (f0 + Fc) hop_s -- that no earlier chunk has emitted; the final chunk emits everything up
+    to (f0 + Fc - 1) hop_s -> (n0, n1, halo)"""
+    n0 = max(0, f0 * hop_s - n_fft // 2)
+    n1 = (f0 + Fc - 1) * hop_s if final else (f0 + Fc) * hop_s - n_fft // 2
+    return n0, max(n0, n1), istft_halo(n_fft, hop_s)
+
+
+def durations_ref(logits):
+    """logits [B, T, nbins] fp32 -> (dur int32 = max(1, round-half-even(sum)), sum fp64 of the sigmoids, the distance of
+    the sum from the nearest half-integer): the duration head in fp64"""
+    s = (1.0 / (1.0 + np.exp(-np.asarray(logits, np.float32).astype(np.float64)))).sum(-1)
+    return np.maximum(np.rint(s), 1).astype(np.int32), s, np.abs(s - np.floor(s) - 0.5)
+
+
+def align_ref(dur, T40):
+    """dur [B, T] int32 (zeros anywhere) -> (idx [B, T40] int32: the token that owns aligned frame f, -1 from the row's
+    own total on; total [B] int32)"""
+    d = np.asarray(dur)
+    idx = np.full((d.shape[0], T40), -1, np.int32)
+    for b in range(d.shape[0]):
+        own = np.repeat(np.arange(d.shape[1], dtype=np.int32), d[b])[:T40]
+        idx[b, :len(own)] = own
+    return idx, d.sum(1).astype(np.int32)
+
+
+E_SIN, E_BM, E_T = 1e-6, 2e-6, 3e-6  # the accuracy claims of csrc/source.hip (sine, Box-Muller) and csrc/istft.hip
+E_RR = 2.0 ** -22                    # the iSTFT's range reduction of a phase argument beyond pi (istft_bound)
+
+
+def source_bound(ref, merge_w, *, n_fft, sine_amp, noise_std):
+    """the per-element bound on fp32 bins against source_ref's dict: d A1 + (n_fft + 4) 2^-24 A2, d = sum_h |mw_h|
+    (sine_amp E_SIN + namp_max E_BM) + 4 2^-24 the per-sample allowance (tanh's slope is at most 1; four roundings of
+    values below 1 in the merge and the tanh), then n_fft accumulation steps of the windowed DFT -> [B, F, 1]"""
+    w = np.abs(np.asarray(merge_w, np.float64)[:-1]).sum()
+    d = w * (sine_amp * E_SIN + max(noise_std, sine_amp / 3.0) * E_BM) + 4 * 2.0 ** -24
+    return (d * ref["A1"] + (n_fft + 4) * 2.0 ** -24 * ref["A2"])[..., None]
+
+
+def istft_bound(S, n_fft, hop_s, reduced):
+    """the per-sample bound against istft_ref's S: (E_T + (nb + halo + 6) 2^-24) S -- three chained hardware
+    transcendentals, nb accumulation steps of the DFT, halo + 1 of the overlap-add, the window, the envelope and the
+    division.  reduced (the large-argument class, |p| up to 2^17): the two-constant reduction xr = fma(-k, lo,
+    fma(-k, hi, p)) rounds twice at |xr| < 4 (half an ulp of 2^-22 each): |d xr| <= 2^-22 = E_RR, which sin, cos and
+    the magnitude carry into the sample with slope at most 1, i.e. as E_RR S."""
+    nb = n_fft // 2 + 1
+    return (E_T + (E_RR if reduced else 0.0) + (nb + istft_halo(n_fft, hop_s) + 6) * 2.0 ** -24) * S
+
+
+def f0_case(B, T80, thr, key):
+    """F0 [B, T80] fp32 for a source case: voiced 80..400 Hz with, where the row is long enough, a stretch of exact
+    zeros, one frame exactly at thr (unvoiced), one at nextafter(thr, inf) (voiced) and one at 900 Hz; shorter rows
+    take these values in turn.  Even rows start and end voiced, odd rows unvoiced (a one-row case by its key)."""
+    g = np.random.default_rng(zlib_key(key))
+    f = g.uniform(80.0, 400.0, (B, T80)).astype(np.float32)
+    special = [np.float32(0.0), np.float32(thr), np.nextafter(np.float32(thr), np.float32(np.inf)), np.float32(900.0)]
+    for b in range(B):
+        if T80 >= 13:
+            f[b, 3:6] = 0.0
+            f[b, 7], f[b, 8], f[b, 9] = special[1], special[2], special[3]
+            if T80 > 40:
+                f[b, T80 // 2:T80 // 2 + 5] = 0.0
+        else:
+            for k in range(T80):
+                f[b, k] = special[(b + k + zlib_key(key)) % 4]
+        if (b + (zlib_key(key) if B == 1 else 0)) % 2 and T80 >= 13:
+            f[b, 0] = f[b, -1] = 0.0
+    return f
+
+
+def zlib_key(key):
+    import zlib
+    return zlib.crc32(repr(key).encode())
+
+
+def post_case(B, Tf, n_fft, cls, key, ldp=None):
+    """conv_post rows [B, Tf, ldp] fp32 for an iSTFT case, NaN beyond the 2 nb used columns: log-magnitudes N(0, 0.5)
+    with one bin at +10 and one at -100 per utterance, phase arguments of class "small" N(0, 2), "mid" N(0, 600) or
+    "large" uniform in +-(2^17 - 1) with two values within 1 of +-2^17"""
+    nb = n_fft // 2 + 1
+    ldp = n_fft + 6 if ldp is None else ldp
+    g = np.random.default_rng(zlib_key(("post",) + tuple(key)))
+    p = np.full((B, Tf, ldp), np.nan, np.float32)
+    p[:, :, :nb] = g.normal(0.0, 0.5, (B, Tf, nb))
+    if cls == "small":
+        p[:, :, nb:2 * nb] = g.normal(0.0, 2.0, (B, Tf, nb))
+    elif cls == "mid":
+        p[:, :, nb:2 * nb] = g.normal(0.0, 600.0, (B, Tf, nb))
+    else:
+        assert cls == "large", cls
+        lim = 2.0 ** 17 - 1
+        p[:, :, nb:2 * nb] = g.uniform(-lim, lim, (B, Tf, nb))
+        p[0, Tf // 2, nb + 1] = np.float32(2.0 ** 17 - 0.5)
+        p[B - 1, Tf - 1, 2 * nb - 1] = np.float32(-(2.0 ** 17) + 0.25)
+    for b in range(B):
+        p[b, (b + 1) % Tf, (3 + b) % nb] = 10.0
+        p[b, (Tf - 1 - b) % Tf, (5 + b) % nb] = -100.0
+    return p
+
+
+# ---- the cases tests/test_gpu_backend.py runs, shared with the CPU self-checks ----
+SHIPPED = dict(hop=300, n_fft=20, hop_s=5, sr=24000.0, sine_amp=0.1, noise_std=0.003, voiced_thr=10.0)
+# the iSTFT geometries of the GPU file, (n_fft, hop_s) -> halo
+ISTFT_GEOMS = {(20, 5): 3, (20, 4): 4, (20, 10): 1, (20, 3): 6, (20, 2): 9, (16, 4): 3, (16, 8): 1, (16, 2): 7}
+# the GPU file's duration shapes and the seed of each (chosen so that the reference alone keeps the tie share < 1 %)
+DUR_NBINS, DUR_ROWS = (1, 7, 8, 9, 50), (1, 255, 256, 257)
+
+
+def merge_weights(nh, key=0):
+    g = np.random.default_rng(1000 + nh + key)
+    return (g.normal(0.0, 0.3, nh + 1)).astype(np.float32)
+
+
+def dur_logits(rows, nbins, seed=0):
+    """[1, rows, nbins] fp32 logits whose sigmoid sums spread over [0, nbins]"""
+    g = np.random.default_rng(77 + 1000 * nbins + rows + seed)
+    return (g.normal(0.0, 2.0, (1, rows, nbins)) + g.normal(0.0, 1.5, (1, rows, 1))).astype(np.float32)
+
+
+def dur_tie_width(nbins):
+    """an fp32 serial sum of nbins sigmoids is within nbins * 2^-23 * nbins of the fp64 sum"""
+    return nbins * 2.0 ** -23 * nbins

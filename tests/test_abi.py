@@ -131,6 +131,62 @@ def test_istft_stream_spans_tile_the_output(Tf, chunks):
     assert L.stzs_istft_stream_span(0, 0, 1, 20, 5, C.byref(n0), C.byref(n1)) == _lib.ESHAPE
 
 
+@pytest.mark.parametrize("n_fft,hop_s", [(20, 5), (20, 4), (20, 10), (20, 3), (20, 2), (16, 4), (16, 8), (16, 2)])
+def test_istft_stream_spans_every_geometry(n_fft, hop_s):
+    """the span query against refops.istft_span_ref (the header's wording restated) for the geometries of
+    tests/test_gpu_backend.py: each chunk's [n0, n1) and the halo value, the chunks tile [0, (Tf - 1) hop_s) without
+    gaps"""
+    from refops import istft_halo, istft_span_ref
+    from stzs import _lib
+    L = _lib.load()
+    halo = istft_halo(n_fft, hop_s)
+    FB = 256 - halo
+    n0, n1 = C.c_int64(), C.c_int64()
+    for chunks in ([1] * 12, [max(halo - 1, 1), 1, 40], [FB, FB, 1], [2, 599], [600, 1], [2], [1, 1]):
+        f0 = nxt = 0
+        for i, Fc in enumerate(chunks):
+            final = int(i == len(chunks) - 1)
+            got = L.stzs_istft_stream_span(f0, Fc, final, n_fft, hop_s, C.byref(n0), C.byref(n1))
+            assert (n0.value, n1.value, got) == istft_span_ref(f0, Fc, final, n_fft, hop_s), (chunks, i)
+            assert got == halo and n0.value == nxt and n1.value >= n0.value
+            nxt = n1.value
+            f0 += Fc
+        assert nxt == (sum(chunks) - 1) * hop_s
+
+
+def test_istft_refuses_hop_equal_to_n_fft():
+    """hop_s == n_fft leaves the padded samples f n_fft under the window's zero tap alone (envelope 0, the sample
+    0 / 0): stzs_istft, stzs_istft_stream and stzs_istft_stream_span return STZS_ESHAPE before any launch, as they do
+    for a transform size other than 16 or 20 (the span query, host arithmetic, takes any even size)"""
+    from stzs import _lib
+    L = _lib.load()
+    n0, n1 = C.c_int64(), C.c_int64()
+    for n_fft, hop_s, launch_ok, span_ok in ((20, 20, 0, 0), (16, 16, 0, 0), (20, 21, 0, 0), (20, 19, 1, 1), (16, 15, 1, 1),
+                                             (32, 8, 0, 1), (18, 3, 0, 1)):
+        rc = L.stzs_istft_stream_span(0, 4, 1, n_fft, hop_s, C.byref(n0), C.byref(n1))
+        assert (rc >= 0) == bool(span_ok) and (span_ok or rc == _lib.ESHAPE), (n_fft, hop_s, rc)
+        if launch_ok:
+            continue  # (an accepted geometry would launch: covered on the GPU)
+        a = _lib.IstftArgs()
+        a.post, a.wav, a.ldp, a.bsp, a.bsw = 0x1000, 0x2000, n_fft + 2, 4 * (n_fft + 2), 3 * hop_s
+        a.B, a.Tf, a.n_fft, a.hop_s = 1, 4, n_fft, hop_s
+        assert L.stzs_istft(C.byref(a), None) == _lib.ESHAPE, (n_fft, hop_s)
+        s = _lib.IstftStreamArgs()
+        s.post, s.wav, s.tail_out, s.ldp, s.bsp, s.bsw, s.ldt = 0x1000, 0x2000, 0x3000, n_fft + 2, 4 * (n_fft + 2), 3 * hop_s, n_fft + 2
+        s.B, s.f0, s.Fc, s.final_chunk, s.n_fft, s.hop_s = 1, 0, 4, 1, n_fft, hop_s
+        assert L.stzs_istft_stream(C.byref(s), None) == _lib.ESHAPE, (n_fft, hop_s)
+
+
+def test_alignment_refuses_T_above_its_limit():
+    """stzs_alignment holds T + 1 scan entries in LDS: T above the documented 16384 returns STZS_ESHAPE before any
+    launch"""
+    from stzs import _lib
+    L = _lib.load()
+    a = _lib.AlignArgs()
+    a.dur, a.idx, a.total, a.B, a.T, a.T40 = 0x1000, 0x2000, 0x3000, 1, 16385, 8
+    assert L.stzs_alignment(C.byref(a), None) == _lib.ESHAPE
+
+
 _STRUCT_CALLS = [  # entry point, ctypes struct, extra int arguments between the struct and the stream
     ("stzs_conv1d", "ConvArgs", ()), ("stzs_chan_stats", "StatsArgs", ()), ("stzs_chan_stats_partial", "StatsArgs", ()),
     ("stzs_chan_stats_final", "StatsArgs", (64,)), ("stzs_row_layernorm", "RowLNArgs", ()),

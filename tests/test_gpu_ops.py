@@ -681,7 +681,14 @@ def test_durations_alignment_gather_exact(eng):
     a.logits, a.override_dur, a.dur, a.dsum = ld.data_ptr(), None, dur.data_ptr(), ds.data_ptr()
     a.ldl, a.bsl, a.B, a.T, a.nbins = nb, T * nb, B, T, nb
     eng._call(eng.lib.stzs_durations, a, "dur")
-    tie = ((dsum - dsum.floor() - 0.5).abs() < 1e-4)
+    # a duration may differ from the oracle's only at a tie, and a tie is derived, not blanket: the fp64 sum of the
+    # sigmoids within nbins * 2^-23 * nbins of a half-integer (what an fp32 serial sum of nbins terms can be off by;
+    # refops.durations_ref) as well as the oracle's own fp32 sum within the 1e-4 this test has always allowed -- and
+    # under 1 % of the elements may be such ties (tests/test_gpu_backend.py runs the shapes around the unrolled loop)
+    from refops import durations_ref
+    dist64 = torch.from_numpy(durations_ref(logits.numpy())[2])
+    tie = ((dsum - dsum.floor() - 0.5).abs() < 1e-4) & (dist64 <= nb * 2.0 ** -23 * nb)
+    assert tie.double().mean().item() < 0.01
     ok = (dur.cpu() == dur_ref) | tie
     assert bool(ok.all())
     # alignment on equal-total durations
