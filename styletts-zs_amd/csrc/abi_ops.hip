@@ -199,8 +199,8 @@ int conv(Ctx& c, const CW& w, const Act& x, const Act& y, const ConvOpt& o = Con
     a.beta = o.beta;
     a.epi_act = o.epi_act;
     a.epi_slope = o.epi_slope;
-    if (w.ks == 1 && o.stride == 1 && o.pad == 0 && !o.pro && o.pro_act == STZS_ACT_NONE && o.cscale == 1.f &&
-        (x.dt == STZS_BF16 || x.dt == STZS_F8) && x.c0 + a.ci_pad <= x.ld && a.T_out == x.T && w.form == STZS_PACK_KSTEP)
+    if (stzs_plain_linear(a) && o.cscale == 1.f && (x.dt == STZS_BF16 || x.dt == STZS_F8) && x.c0 + a.ci_pad <= x.ld &&
+        w.form == STZS_PACK_KSTEP)
         a.flags |= STZS_CONV_A_DMA;
     if (o.rows && rows_ok(a.ci_pad) && w.ks == 1 && w.form == STZS_PACK_KSTEP && !o.pro && !o.stats_out &&
         (x.dt == STZS_F32 || (x.dt == STZS_BF16 && o.cscale == 1.f)) && x.c0 + a.ci_pad <= x.ld && a.T_out == x.T)
@@ -495,9 +495,7 @@ int denoiser(Ctx& c, const stzs_tensor_t* in, int n_in, stzs_tensor_t* out, int 
             f.v[j] = (float)cos(arg);
             f.v[half + j] = (float)sin(arg);
         }
-        hipLaunchKernelGGL(four_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(c.stream), f,
-                           (float*)four.ptr(), nf);
-        if (hipGetLastError() != hipSuccess) return STZS_EHIP;
+        CK(stzs_launch(four_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(c.stream), f, (float*)four.ptr(), nf));
     }
     {
         ConvOpt o;

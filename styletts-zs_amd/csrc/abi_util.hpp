@@ -6,7 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.hpp"
+#include "conv_args.hpp"
 
 namespace stzs_abi {
 

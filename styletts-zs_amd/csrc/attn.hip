@@ -183,22 +183,18 @@ extern "C" int stzs_attention(const stzs_attn_args* a, void* stream) {
     if (a->precise == 1) {
         dim3 g((unsigned)a->R, a->heads, (a->Lq + 63) / 64);
         if (a->dh == 64)
-            hipLaunchKernelGGL(attn_x3<64>, g, dim3(256), 0, s, *a);
+            return stzs_launch(attn_x3<64>, g, dim3(256), 0, s, *a);
         else if (a->dh == 32)
-            hipLaunchKernelGGL(attn_x3<32>, g, dim3(256), 0, s, *a);
+            return stzs_launch(attn_x3<32>, g, dim3(256), 0, s, *a);
         else
             return STZS_ESHAPE;
-        STZS_LAUNCH_CHECK();
-        return STZS_OK;
     }
     if (a->precise != 0) return STZS_EINVAL;
     dim3 g((unsigned)a->R, a->heads, (a->Lq + 63) / 64);
     if (a->dh == 64)
-        hipLaunchKernelGGL(attn_mfma<64>, g, dim3(256), 0, s, *a);
+        return stzs_launch(attn_mfma<64>, g, dim3(256), 0, s, *a);
     else if (a->dh == 32)
-        hipLaunchKernelGGL(attn_mfma<32>, g, dim3(256), 0, s, *a);
+        return stzs_launch(attn_mfma<32>, g, dim3(256), 0, s, *a);
     else
         return STZS_ESHAPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }

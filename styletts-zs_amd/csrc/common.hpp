@@ -154,11 +154,17 @@ STZS_DEV float wave_max(float v) {
     return v;
 }
 
-#define STZS_LAUNCH_CHECK()                                          \
-    do {                                                             \
-        hipError_t e__ = hipGetLastError();                          \
-        if (e__ != hipSuccess) return STZS_EHIP;                     \
-    } while (0)
+// Every kernel launch of the library: the dynamic-LDS limit raised first where the launch asks for more than the
+// 64 KB a kernel may use without it (a refused attribute is an error, never a launch), then the launch, its error as a
+// library code.  `args` are copied into the kernel's by-value parameters.
+template <typename... P, typename... A>
+static inline int stzs_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return STZS_EHIP;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return hipGetLastError() == hipSuccess ? STZS_OK : STZS_EHIP;
+}
 
 static inline bool stzs_aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 

@@ -530,8 +530,7 @@ size_t lds_bytes(int rows_in, int cic, int nslot = NSLOT) {
 
 template <typename TIn, typename TOut, bool F8 = false>
 int launch_dt(const stzs_conv_args& a, hipStream_t s) {
-    const bool flat = (a.ks == 1 && a.stride == 1 && a.pad == 0 && a.ups == 0 && a.pro_mode == STZS_PRO_NONE &&
-                       a.pro_act == STZS_ACT_NONE && a.T_in == a.T_out);
+    const bool flat = stzs_plain_linear(a);
     const int rows_in = flat ? BT : (BT - 1) * a.stride + (a.ks - 1) * a.dil + 1;
     // DEEP: split-K with one input-channel chunk per slice whose K-steps all fit LDS beside the staged rows
     const int nslot_deep = (flat ? 1 : a.ks) * (a.cic >> 5);
@@ -566,13 +565,10 @@ int launch_dt(const stzs_conv_args& a, hipStream_t s) {
                 k = conv_mfma<TIn, TOut, false, STZS_ACT_SNAKE, true, true>;
             else
                 k = conv_mfma<TIn, TOut, false, STZS_ACT_NONE, true, true>;
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(k, grid, dim3(NTHR), lds, s, a);
-            STZS_LAUNCH_CHECK();
+            const int rc = stzs_launch(k, grid, dim3(NTHR), lds, s, a);
+            if (rc != STZS_OK) return rc;
             auto ke = flat ? splitk_epi<TOut, true> : splitk_epi<TOut, false>;
-            hipLaunchKernelGGL(ke, dim3(grid.x, grid.y * 8), dim3(NTHR), 0, s, a, (int)a.splitk);
-            STZS_LAUNCH_CHECK();
-            return STZS_OK;
+            return stzs_launch(ke, dim3(grid.x, grid.y * 8), dim3(NTHR), 0, s, a, (int)a.splitk);
         }
         if (deep) {
             if (flat)
@@ -591,10 +587,7 @@ int launch_dt(const stzs_conv_args& a, hipStream_t s) {
             k = conv_mfma<TIn, TOut, false, STZS_ACT_LEAKY>;
         else
             k = conv_mfma<TIn, TOut, false, STZS_ACT_NONE>;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, grid, dim3(NTHR), lds, s, a);
-        STZS_LAUNCH_CHECK();
-        return STZS_OK;
+        return stzs_launch(k, grid, dim3(NTHR), lds, s, a);
     }
 }
 
@@ -606,8 +599,7 @@ int launch_pair_dt(const stzs_conv_args* p, hipStream_t s) {
     size_t lds = 0;
     for (int i = 0; i < 2; ++i) {
         const stzs_conv_args& a = p[i];
-        const bool flat = (a.ks == 1 && a.stride == 1 && a.pad == 0 && a.ups == 0 && a.pro_mode == STZS_PRO_NONE &&
-                           a.pro_act == STZS_ACT_NONE && a.T_in == a.T_out);
+        const bool flat = stzs_plain_linear(a);
         const int rows_in = (BT - 1) * a.stride + (a.ks - 1) * a.dil + 1;
         const int nslot_deep = a.ks * (a.cic >> 5);
         const bool deep = !flat && a.splitk > 1 && a.splitk == a.ci_pad / a.cic && !(a.flags & STZS_CONV_RING) &&
@@ -626,13 +618,10 @@ int launch_pair_dt(const stzs_conv_args* p, hipStream_t s) {
     void (*k)(stzs_conv_args, stzs_conv_args) = a.pro_act == STZS_ACT_LEAKY ? conv_mfma_pair<TIn, TOut, STZS_ACT_LEAKY>
                                                : a.pro_act == STZS_ACT_SNAKE ? conv_mfma_pair<TIn, TOut, STZS_ACT_SNAKE>
                                                                              : conv_mfma_pair<TIn, TOut, STZS_ACT_NONE>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid((unsigned)a.B * (unsigned)((a.T_out + BT - 1) / BT), a.co_pad / BCO, 2 * a.splitk);
-    hipLaunchKernelGGL(k, grid, dim3(NTHR), lds, s, p[0], p[1]);
-    STZS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(splitk_epi_pair<TOut>, dim3(grid.x, grid.y * 8, 2), dim3(NTHR), 0, s, p[0], p[1], (int)a.splitk);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    const int rc = stzs_launch(k, grid, dim3(NTHR), lds, s, p[0], p[1]);
+    if (rc != STZS_OK) return rc;
+    return stzs_launch(splitk_epi_pair<TOut>, dim3(grid.x, grid.y * 8, 2), dim3(NTHR), 0, s, p[0], p[1], (int)a.splitk);
 }
 
 }  // namespace
@@ -642,20 +631,14 @@ int stzs_narrow_conv_launch(const stzs_conv_args& a, hipStream_t s);  // csrc/mr
 
 namespace {
 
+// what the kernel families behind stzs_conv1d_core ask beyond stzs_conv_check (csrc/dispatch.hip): input channels in
+// chunks of cic, the ConvTranspose geometry, the residual's time divisor, the prologue partials and activation, the
+// fused statistics' vector epilogue
 int core_checks(const stzs_conv_args* a) {
-    if (!a || !a->x || !a->w || !a->y) return STZS_EINVAL;
     if (a->cic != 32 && a->cic != 64 && a->cic != 128) return STZS_EINVAL;
-    if (a->B <= 0 || a->T_in <= 0 || a->T_out <= 0 || a->Ci <= 0 || a->Co <= 0 || a->ks <= 0 || a->dil <= 0 ||
-        a->stride <= 0)
-        return STZS_ESHAPE;
-    if (a->ci_pad % a->cic || a->ci_pad < a->Ci || a->co_pad % BCO) return STZS_ESHAPE;
-    if (a->splitk > 1 && (a->flags & (STZS_CONV_W_X3 | STZS_CONV_W_F32 | STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32)))
-        return STZS_EINVAL;
-    const int ncol = a->ups > 0 ? a->ups * a->Co : a->Co;
-    if (a->co_pad < ncol) return STZS_ESHAPE;
-    if (a->ldx % 8 || a->bsx % 8 || a->ldx < ((a->Ci + 7) / 8) * 8) return STZS_ESHAPE;
-    if (!stzs_aligned(a->x, 16) || !stzs_aligned(a->w, 16)) return STZS_EINVAL;
+    if (a->ci_pad % a->cic) return STZS_ESHAPE;
     if (a->ups > 0) {
+        if (a->co_pad < a->ups * a->Co) return STZS_ESHAPE;
         if (a->ks != 2 || a->pad != 1 || a->stride != 1 || a->dil != 1 || a->T_out != a->T_in + 1) return STZS_ESHAPE;
         if (a->Co % 8) return STZS_ESHAPE;
         if (a->refl && a->T_final < 2) return STZS_ESHAPE;
@@ -663,18 +646,12 @@ int core_checks(const stzs_conv_args* a) {
         return STZS_EINVAL;
     }
     if (a->res && a->res_tdiv <= 0) return STZS_EINVAL;
-    if (a->pro_part && (a->pro_nch < 1 || a->pro_nch > 8 || a->pro_T < 1 || a->pro_ld < a->Ci ||
-                        (a->flags & (STZS_CONV_W_X3 | STZS_CONV_W_F32 | STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 |
-                                     STZS_CONV_W_FRAG32 | STZS_CONV_W_FRAG32X3 | STZS_CONV_ROWS | STZS_CONV_A_DMA))))
-        return STZS_EINVAL;  // (the prologue partials: generic conv path, <= 8 chunks)
-    if (a->pro_mode == STZS_PRO_ADAIN && (!a->pro_part && (!a->pro_mean || !a->pro_rstd)) ) return STZS_EINVAL;
-    if (a->pro_mode == STZS_PRO_ADAIN && !a->pro_gb) return STZS_EINVAL;
+    if (a->pro_part && (a->pro_nch < 1 || a->pro_nch > 8 || a->pro_T < 1 || a->pro_ld < a->Ci))
+        return STZS_EINVAL;  // (the prologue partials: <= 8 chunks)
     // the prologue activations: NONE, LEAKY, SNAKE only (GELU / SILU are epilogue activations); every kernel family
     // below selects its prologue template from these three
     if (a->pro_act != STZS_ACT_NONE && a->pro_act != STZS_ACT_LEAKY && a->pro_act != STZS_ACT_SNAKE) return STZS_EINVAL;
-    if (a->pro_act == STZS_ACT_SNAKE && !a->pro_alpha) return STZS_EINVAL;
-    if (a->stat_part && (a->ups > 0 || !epi_vec(*a) || a->stat_ld < a->Co || !stzs_aligned(a->stat_part, 8)))
-        return STZS_EINVAL;
+    if (a->stat_part && (a->ups > 0 || !epi_vec(*a) || a->stat_ld < a->Co)) return STZS_EINVAL;
     return STZS_OK;
 }
 
@@ -684,17 +661,19 @@ int core_checks(const stzs_conv_args* a) {
 // pass stzs_conv1d's checks, be bf16 -> bf16 without a W_* / ROWS / A_DMA flag and take the DEEP split-K form with the
 // splitk_epi combine on its own; STZS_ESHAPE otherwise (nothing launched: the caller runs them one at a time).
 __attribute__((visibility("hidden"))) int stzs_conv_pair_launch(const stzs_conv_args* p, hipStream_t s) {
-    constexpr int WF = STZS_CONV_W_X3 | STZS_CONV_W_F32 | STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_FRAG32 |
-                       STZS_CONV_W_FRAG32X3 | STZS_CONV_ROWS | STZS_CONV_A_DMA | STZS_CONV_UPS_NOISE;
     for (int i = 0; i < 2; ++i) {
-        const int rc = core_checks(&p[i]);
+        int rc = stzs_conv_check(&p[i]);
+        if (rc == STZS_OK) rc = core_checks(&p[i]);
         if (rc != STZS_OK) return rc;
-        if ((p[i].flags & WF) || p[i].in_dtype != STZS_BF16 || p[i].out_dtype != STZS_BF16) return STZS_ESHAPE;
+        if ((p[i].flags & (STZS_CONV_NOT_GENERIC | STZS_CONV_UPS_NOISE)) || p[i].in_dtype != STZS_BF16 ||
+            p[i].out_dtype != STZS_BF16)
+            return STZS_ESHAPE;
     }
     return launch_pair_dt<bf16_t, bf16_t>(p, s);
 }
 
-// the dispatcher proper; csrc/dispatch.hip routes the register-direct MRF form before it
+// the dispatcher proper; csrc/dispatch.hip has validated the form-independent part (stzs_conv_check) and routes the
+// register-direct and ROWS forms before it
 __attribute__((visibility("hidden"))) int stzs_conv1d_core(const stzs_conv_args* a, void* stream) {
     {
         const int rc = core_checks(a);
@@ -702,8 +681,7 @@ __attribute__((visibility("hidden"))) int stzs_conv1d_core(const stzs_conv_args*
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a->in_dtype == STZS_F8) {
-        const bool lin = a->ks == 1 && a->stride == 1 && a->pad == 0 && a->ups == 0 && a->T_in == a->T_out &&
-                         a->pro_mode == STZS_PRO_NONE && a->pro_act == STZS_ACT_NONE && a->pro_cscale == 1.f;
+        const bool lin = stzs_plain_linear(*a) && a->pro_cscale == 1.f;  // (fp8 rows carry their own scale)
         if (!lin || !(a->flags & STZS_CONV_A_DMA) || (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32)))
             return STZS_EDTYPE;
         if (!a->x_scale || !a->w_scale || a->stat_part) return STZS_EINVAL;
@@ -730,7 +708,7 @@ extern "C" size_t stzs_conv_splitk_workspace(int64_t rows, int32_t co_pad, int32
 }
 
 #ifdef STZS_GEMM_PROF
-extern "C" int stzs_gemm_prof_conv(const stzs_conv_args* a, void* stream) { return stzs_conv1d_core(a, stream); }
+extern "C" int stzs_gemm_prof_conv(const stzs_conv_args* a, void* stream) { return stzs_conv1d(a, stream); }
 #endif
 
 #ifdef STZS_CONV_PROF

@@ -2,7 +2,7 @@
 // csrc/convx.hip conv_f32 / conv_x3): tile constants, the prologue activations, the staged-row readers and the fused
 // LDS epilogue (finish).  Each including file gets its own internal copy (anonymous namespace).
 #pragma once
-#include "common.hpp"
+#include "conv_args.hpp"
 
 namespace {
 

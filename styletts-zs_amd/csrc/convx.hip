@@ -278,42 +278,37 @@ size_t x3_lds_bytes(int rows_in) {
     return main > epi ? main : epi;
 }
 
+// the conv_x3 instance of a launch (FLAT: no prologue activation)
+template <typename TI, typename TO>
+void (*pick_x3(bool flat, int pro_act))(stzs_conv_args) {
+    return flat                         ? conv_x3<TI, TO, STZS_ACT_NONE, true>
+           : pro_act == STZS_ACT_SNAKE ? conv_x3<TI, TO, STZS_ACT_SNAKE, false>
+           : pro_act == STZS_ACT_LEAKY ? conv_x3<TI, TO, STZS_ACT_LEAKY, false>
+                                       : conv_x3<TI, TO, STZS_ACT_NONE, false>;
+}
+
 }  // namespace
 
 // internal entries (csrc/conv.hip stzs_conv1d_core, arguments validated there)
 __attribute__((visibility("hidden"))) int stzs_conv_x3_launch(const stzs_conv_args* a, hipStream_t s) {
-    if (a->cic != 32 || a->ci_pad % 32 || (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32)))
-        return STZS_EINVAL;
-    if (a->in_dtype == STZS_F32 ? (a->ldx % 8 || a->bsx % 8) : false) return STZS_ESHAPE;
+    if (a->cic != 32 || a->ci_pad % 32) return STZS_EINVAL;
     const int rows_in = (BT - 1) * a->stride + (a->ks - 1) * a->dil + 1;
     const size_t lds = x3_lds_bytes(rows_in);
     if (lds > 160 * 1024) return STZS_ESHAPE;
     void (*k)(stzs_conv_args) = nullptr;
-    const bool flat = a->ks == 1 && a->stride == 1 && a->pad == 0 && a->ups == 0 && a->pro_mode == STZS_PRO_NONE &&
-                      a->pro_act == STZS_ACT_NONE && a->T_in == a->T_out && !a->stat_part;
-#define STZS_X3_PICK(TI, TO)                                                                         \
-    k = flat ? conv_x3<TI, TO, STZS_ACT_NONE, true>                                                  \
-    : a->pro_act == STZS_ACT_SNAKE ? conv_x3<TI, TO, STZS_ACT_SNAKE, false>                      \
-    : a->pro_act == STZS_ACT_LEAKY ? conv_x3<TI, TO, STZS_ACT_LEAKY, false> : conv_x3<TI, TO, STZS_ACT_NONE, false>;
-    if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32) { STZS_X3_PICK(float, float) }
-    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16) { STZS_X3_PICK(float, bf16_t) }
-    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32) { STZS_X3_PICK(bf16_t, float) }
-    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16) { STZS_X3_PICK(bf16_t, bf16_t) }
+    const bool flat = stzs_plain_linear(*a) && !a->stat_part;  // (fused statistics: per-utterance tiles only)
+    if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32) k = pick_x3<float, float>(flat, a->pro_act);
+    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16) k = pick_x3<float, bf16_t>(flat, a->pro_act);
+    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32) k = pick_x3<bf16_t, float>(flat, a->pro_act);
+    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16) k = pick_x3<bf16_t, bf16_t>(flat, a->pro_act);
     else return STZS_EDTYPE;
-#undef STZS_X3_PICK
-    if (a->pro_act != STZS_ACT_NONE && a->pro_act != STZS_ACT_LEAKY && a->pro_act != STZS_ACT_SNAKE)
-        return STZS_EINVAL;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid(flat ? (unsigned)(((long)a->B * a->T_out + BT - 1) / BT)
                    : (unsigned)a->B * (unsigned)((a->T_out + BT - 1) / BT), a->co_pad / BCO);
-    hipLaunchKernelGGL(k, grid, dim3(NTHR), lds, s, *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(k, grid, dim3(NTHR), lds, s, *a);
 }
 
 __attribute__((visibility("hidden"))) int stzs_conv_f32_launch(const stzs_conv_args* a, hipStream_t s) {
-    if (a->cic != 32 || a->ci_pad % 32 || (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32)))
-        return STZS_EINVAL;
+    if (a->cic != 32 || a->ci_pad % 32) return STZS_EINVAL;
     const int rows_in = (BT - 1) * a->stride + (a->ks - 1) * a->dil + 1;
     const size_t main = (size_t)(rows_in + BCO) * P32 * 4;
     const size_t epi = (size_t)BT * EP_PITCH * 4 + 2 * BCO * 4 + 2 * 4 * BCO * 2 * 4;
@@ -325,9 +320,6 @@ __attribute__((visibility("hidden"))) int stzs_conv_f32_launch(const stzs_conv_a
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32) k = conv_f32<bf16_t, float>;
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16) k = conv_f32<bf16_t, bf16_t>;
     else return STZS_EDTYPE;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid((unsigned)a->B * (unsigned)((a->T_out + BT - 1) / BT), a->co_pad / BCO);
-    hipLaunchKernelGGL(k, grid, dim3(NTHR), lds, s, *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(k, grid, dim3(NTHR), lds, s, *a);
 }

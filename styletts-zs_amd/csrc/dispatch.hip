@@ -1,8 +1,7 @@
-// stzs_conv1d entry (include/stzs.h): argument checks shared by every conv form, then the
-// register-direct MRF conv (csrc/mrfv.hip) for STZS_CONV_W_FRAG32 weights, the general dispatcher
-// (csrc/conv.hip) for everything else.  Kept in its own translation unit so that adding a kernel
-// form does not rebuild conv.hip.
-#include "common.hpp"
+// stzs_conv1d / stzs_conv1d_group entries (include/stzs.h): the argument checks shared by every conv form
+// (stzs_conv_check), then the form's launcher by the table of csrc/conv_args.hpp.  Kept in its own translation unit
+// so that adding a kernel form does not rebuild conv.hip.
+#include "conv_args.hpp"
 
 int stzs_conv1d_core(const stzs_conv_args* a, void* stream);           // csrc/conv.hip
 int stzs_mrfv_conv_launch(const stzs_conv_args& a, hipStream_t s);    // csrc/mrfv.hip
@@ -12,32 +11,32 @@ int stzs_mrfx_conv_launch(const stzs_conv_args& a, hipStream_t s);    // csrc/mr
 int stzs_mrfv_trio_launch(const stzs_conv_args* a, hipStream_t s);   // csrc/mrfv.hip
 int stzs_conv_pair_launch(const stzs_conv_args* a, hipStream_t s);    // csrc/conv.hip
 
-namespace {
-
-// stzs_conv1d's argument checks for STZS_CONV_W_FRAG32 weights (the register-direct conv)
-int frag32_checks(const stzs_conv_args* a) {
-    if (!a->x || !a->w || !a->y) return STZS_EINVAL;
-    if (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32 | STZS_CONV_A_DMA)) return STZS_EINVAL;
-    if (a->B <= 0 || a->T_in <= 0 || a->T_out <= 0 || a->Ci <= 0 || a->Co <= 0 || a->dil <= 0) return STZS_ESHAPE;
+__attribute__((visibility("hidden"))) int stzs_conv_check(const stzs_conv_args* a) {
+    if (!a || !a->x || !a->w || !a->y) return STZS_EINVAL;
+    const stzs_conv_form& f = stzs_conv_form_of(a->flags);
+    if (a->flags & f.excludes) return STZS_EINVAL;
+    if (a->pro_part && (a->flags & STZS_CONV_NOT_GENERIC)) return STZS_EINVAL;  // (the generic conv path only)
+    if (a->B <= 0 || a->T_in <= 0 || a->T_out <= 0 || a->Ci <= 0 || a->Co <= 0) return STZS_ESHAPE;
+    if (f.taps && (a->ks <= 0 || a->dil <= 0 || a->stride <= 0)) return STZS_ESHAPE;
     if (a->ci_pad < a->Ci || a->co_pad < a->Co) return STZS_ESHAPE;
+    // output channels in tiles of 128 (but the polyphase ConvTranspose, csrc/ups.hip, which tiles ups x Co itself)
+    if (a->co_pad % 128 && !(f.bit == STZS_CONV_W_FRAG32 && a->ups > 0)) return STZS_ESHAPE;
+    // input rows are read as 16-byte vectors of 8 bf16 channels (32-byte ones of fp32: the precise forms' own check)
     if (a->ldx % 8 || a->bsx % 8 || a->ldx < ((a->Ci + 7) / 8) * 8) return STZS_ESHAPE;
-    if (!stzs_aligned(a->x, 16) || !stzs_aligned(a->w, 16) || !stzs_aligned(a->y, 16)) return STZS_EINVAL;
-    if (a->pro_mode == STZS_PRO_ADAIN && (!a->pro_mean || !a->pro_rstd || !a->pro_gb)) return STZS_EINVAL;
-    if (a->in_dtype == STZS_F8 || a->x_scale) return STZS_EDTYPE;
-    if (a->splitk > 1) return STZS_EINVAL;
+    if (!stzs_aligned(a->x, 16) || !stzs_aligned(a->w, 16)) return STZS_EINVAL;
+    if (a->pro_mode == STZS_PRO_ADAIN && ((!a->pro_part && (!a->pro_mean || !a->pro_rstd)) || !a->pro_gb)) return STZS_EINVAL;
+    if (a->pro_act == STZS_ACT_SNAKE && !a->pro_alpha) return STZS_EINVAL;
     if (a->stat_part && !stzs_aligned(a->stat_part, 8)) return STZS_EINVAL;
+    if (a->splitk > 1 && !f.splitk) return STZS_EINVAL;
     return STZS_OK;
 }
 
-}  // namespace
-
 extern "C" int stzs_conv1d_group(const stzs_conv_args* a, int n, void* stream) {
     if (!a || n < 1 || n > 3) return STZS_EINVAL;
-    if (n == 3 && !a[0].pro_part && !a[1].pro_part && !a[2].pro_part && (a[0].flags & STZS_CONV_W_FRAG32) &&
-        (a[1].flags & STZS_CONV_W_FRAG32) && (a[2].flags & STZS_CONV_W_FRAG32) && !(a[0].flags & STZS_CONV_W_FRAG32X3) &&
-        !(a[1].flags & STZS_CONV_W_FRAG32X3) && !(a[2].flags & STZS_CONV_W_FRAG32X3) && a[0].ups <= 0 && a[1].ups <= 0 &&
-        a[2].ups <= 0 && frag32_checks(&a[0]) == STZS_OK && frag32_checks(&a[1]) == STZS_OK &&
-        frag32_checks(&a[2]) == STZS_OK) {
+    const auto trio_member = [](const stzs_conv_args& p) {  // a valid FRAG32 conv (not the ConvTranspose form)
+        return stzs_conv_form_of(p.flags).bit == STZS_CONV_W_FRAG32 && p.ups <= 0 && stzs_conv_check(&p) == STZS_OK;
+    };
+    if (n == 3 && trio_member(a[0]) && trio_member(a[1]) && trio_member(a[2])) {
         const int rc = stzs_mrfv_trio_launch(a, reinterpret_cast<hipStream_t>(stream));
         if (rc == STZS_OK) return 1;
         if (rc != STZS_ESHAPE) return rc;
@@ -55,35 +54,13 @@ extern "C" int stzs_conv1d_group(const stzs_conv_args* a, int n, void* stream) {
 }
 
 extern "C" int stzs_conv1d(const stzs_conv_args* a, void* stream) {
-    // prologue statistics from partials (pro_part): the generic conv path only (csrc/conv.hip checks the rest)
-    if (a && a->pro_part && (a->flags & (STZS_CONV_W_FRAG32X3 | STZS_CONV_W_FRAG32 | STZS_CONV_ROWS))) return STZS_EINVAL;
-    if (a && (a->flags & STZS_CONV_W_FRAG32X3)) {  // the precise register-direct form
-        if (!a->x || !a->w || !a->y) return STZS_EINVAL;
-        if (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32 | STZS_CONV_W_X3 | STZS_CONV_A_DMA |
-                        STZS_CONV_W_FRAG32 | STZS_CONV_ROWS | STZS_CONV_UPS_NOISE))
-            return STZS_EINVAL;
-        if (a->B <= 0 || a->T_in <= 0 || a->T_out <= 0 || a->Ci <= 0 || a->Co <= 0 || a->dil <= 0) return STZS_ESHAPE;
-        if (a->ci_pad < a->Ci || a->co_pad < a->Co || a->ldx < ((a->Ci + 7) / 8) * 8) return STZS_ESHAPE;
-        if (!stzs_aligned(a->w, 16)) return STZS_EINVAL;
-        if (a->pro_mode == STZS_PRO_ADAIN && (!a->pro_mean || !a->pro_rstd || !a->pro_gb)) return STZS_EINVAL;
-        if (a->in_dtype == STZS_F8 || a->x_scale) return STZS_EDTYPE;
-        if (a->splitk > 1) return STZS_EINVAL;
-        if (a->stat_part && !stzs_aligned(a->stat_part, 8)) return STZS_EINVAL;
-        return stzs_mrfx_conv_launch(*a, reinterpret_cast<hipStream_t>(stream));
+    const int rc = stzs_conv_check(a);
+    if (rc != STZS_OK) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (stzs_conv_form_of(a->flags).bit) {
+        case STZS_CONV_W_FRAG32X3: return stzs_mrfx_conv_launch(*a, s);  // the precise register-direct form
+        case STZS_CONV_W_FRAG32: return stzs_mrfv_conv_launch(*a, s);
+        case STZS_CONV_ROWS: return stzs_rows_gemm_launch(*a, s);
+        default: return stzs_conv1d_core(a, stream);
     }
-    if (a && (a->flags & STZS_CONV_W_FRAG32)) {
-        const int rc = frag32_checks(a);
-        if (rc != STZS_OK) return rc;
-        return stzs_mrfv_conv_launch(*a, reinterpret_cast<hipStream_t>(stream));
-    }
-    if (a && (a->flags & STZS_CONV_ROWS)) {
-        if (!a->x || !a->w || !a->y) return STZS_EINVAL;
-        if (a->B <= 0 || a->T_in <= 0 || a->T_out <= 0 || a->Ci <= 0 || a->Co <= 0) return STZS_ESHAPE;
-        if (a->ci_pad < a->Ci || a->co_pad < a->Co || a->co_pad % 128) return STZS_ESHAPE;
-        if (a->ldx % 8 || a->bsx % 8) return STZS_ESHAPE;
-        if (!stzs_aligned(a->x, 16) || !stzs_aligned(a->w, 16)) return STZS_EINVAL;
-        if (a->res && a->res_tdiv != 1) return STZS_EINVAL;  // the residual row is the output row (rows.hip)
-        return stzs_rows_gemm_launch(*a, reinterpret_cast<hipStream_t>(stream));
-    }
-    return stzs_conv1d_core(a, stream);
 }

@@ -148,13 +148,11 @@ extern "C" int stzs_code_quantize(const stzs_vq_args* a, void* stream) {
     const size_t lds = (size_t)a->K * a->dg * 4 + VQ_WAVES * 64 * 8;
     if (lds > 64 * 1024) return STZS_ESHAPE;  // codebook of one group staged in LDS
     switch (a->dg) {
-        case 4: hipLaunchKernelGGL(vq_kernel<4>, g, dim3(64 * VQ_WAVES), lds, s, *a); break;
-        case 8: hipLaunchKernelGGL(vq_kernel<8>, g, dim3(64 * VQ_WAVES), lds, s, *a); break;
-        case 16: hipLaunchKernelGGL(vq_kernel<16>, g, dim3(64 * VQ_WAVES), lds, s, *a); break;
+        case 4: return stzs_launch(vq_kernel<4>, g, dim3(64 * VQ_WAVES), lds, s, *a);
+        case 8: return stzs_launch(vq_kernel<8>, g, dim3(64 * VQ_WAVES), lds, s, *a);
+        case 16: return stzs_launch(vq_kernel<16>, g, dim3(64 * VQ_WAVES), lds, s, *a);
         default: return STZS_ESHAPE;
     }
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_stft_frames(const stzs_frames_args* a, void* stream) {
@@ -163,9 +161,7 @@ extern "C" int stzs_stft_frames(const stzs_frames_args* a, void* stream) {
         a->ldy % 8 || a->n_fft / 2 >= a->N)
         return STZS_ESHAPE;  // reflect padding needs N > n_fft / 2 (as torch)
     if ((long)(a->F - 1) * a->hop > (long)a->N + a->n_fft) return STZS_ESHAPE;
-    hipLaunchKernelGGL(frames_kernel, dim3(a->F, a->B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(frames_kernel, dim3(a->F, a->B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
 }
 
 extern "C" int stzs_log_mel(const stzs_logmel_args* a, void* stream) {
@@ -174,10 +170,8 @@ extern "C" int stzs_log_mel(const stzs_logmel_args* a, void* stream) {
         a->ldy < a->n_mels)
         return STZS_ESHAPE;
     if (a->out_dtype != STZS_BF16 && a->out_dtype != STZS_F32) return STZS_EDTYPE;
-    hipLaunchKernelGGL(log_mel_kernel, dim3(a->F, a->B), dim3(256), (size_t)a->nbin * 4,
+    return stzs_launch(log_mel_kernel, dim3(a->F, a->B), dim3(256), (size_t)a->nbin * 4,
                        reinterpret_cast<hipStream_t>(stream), *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_pool_rows(const stzs_pool_args* a, void* stream) {
@@ -186,15 +180,13 @@ extern "C" int stzs_pool_rows(const stzs_pool_args* a, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 g(a->L, a->B);
     if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16)
-        hipLaunchKernelGGL((pool_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, *a);
+        return stzs_launch((pool_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, *a);
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL((pool_kernel<bf16_t, float>), g, dim3(256), 0, s, *a);
+        return stzs_launch((pool_kernel<bf16_t, float>), g, dim3(256), 0, s, *a);
     else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL((pool_kernel<float, float>), g, dim3(256), 0, s, *a);
+        return stzs_launch((pool_kernel<float, float>), g, dim3(256), 0, s, *a);
     else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16)
-        hipLaunchKernelGGL((pool_kernel<float, bf16_t>), g, dim3(256), 0, s, *a);
+        return stzs_launch((pool_kernel<float, bf16_t>), g, dim3(256), 0, s, *a);
     else
         return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }

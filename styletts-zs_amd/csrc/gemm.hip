@@ -279,10 +279,7 @@ int gemm_launch(const stzs_conv_args& a, hipStream_t s) {
         lg = gemm_lds<64>();
     }
     if (small) grid.x = (unsigned)(((long)a.B * a.T_out + 63) / 64);
-    (void)hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lg);
-    hipLaunchKernelGGL(kg, grid, dim3(NTHR), lg, s, a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(kg, grid, dim3(NTHR), lg, s, a);
 }
 
 }  // namespace

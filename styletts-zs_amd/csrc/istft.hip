@@ -148,13 +148,11 @@ int launch(const IstftJob& j, int nfft, int B, long m_lo, hipStream_t s) {
     if (nblk < nblk_f) nblk = nblk_f;
     dim3 g((unsigned)nblk, B);
     if (nfft == 20)
-        hipLaunchKernelGGL(istft_kernel<20>, g, dim3(256), lds, s, j);
+        return stzs_launch(istft_kernel<20>, g, dim3(256), lds, s, j);
     else if (nfft == 16)
-        hipLaunchKernelGGL(istft_kernel<16>, g, dim3(256), lds, s, j);
+        return stzs_launch(istft_kernel<16>, g, dim3(256), lds, s, j);
     else
         return STZS_ESHAPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 // hop_s == n_fft is refused: the padded samples f * n_fft would be covered by the zero tap win[0] alone (envelope 0,

@@ -298,16 +298,19 @@ void* pick(int nk, int act) {
 
 }  // namespace
 
+// stzs_ln_linear takes KSTEP-packed weights only: the other weight forms' bits are an error (the routing bits
+// STZS_CONV_ROWS / STZS_CONV_A_DMA, which the engine leaves set on a struct it also passes to stzs_conv1d, are not)
+constexpr int LN_LINEAR_EXCLUDES = STZS_CONV_OLD_FORMS | STZS_CONV_W_X3 | STZS_CONV_W_FRAG32 | STZS_CONV_UPS_NOISE;
+
 // (the K-slice form's slabs: ceil(M / 16) x ceil(Co / 64) tiles x Z x 4 KB, which stzs_conv_rows_workspace(M, Co, Z)
 // covers (it returns the larger of this layout and csrc/rows.hip's); its tickets: one per tile)
 static int plain_launch(const stzs_conv_args* a, hipStream_t s) {
     if (!a->x) return STZS_EINVAL;
-    const bool lin = a->ks == 1 && a->stride == 1 && a->pad == 0 && a->ups == 0 && a->T_in == a->T_out &&
-                     a->pro_mode == STZS_PRO_NONE && a->pro_act == STZS_ACT_NONE && !a->stat_part && !a->x_scale &&
+    // a plain linear without fused statistics or an fp8 row scale, unsliced or in 2 / 4 K slices, the residual row the
+    // output row
+    const bool lin = stzs_plain_linear(*a) && !a->stat_part && !a->x_scale &&
                      (a->splitk <= 1 || a->splitk == 2 || a->splitk == 4) && (!a->res || a->res_tdiv == 1);
-    if (!lin || (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32 | STZS_CONV_W_X3 |
-                             STZS_CONV_W_FRAG32 | STZS_CONV_UPS_NOISE)))
-        return STZS_EINVAL;
+    if (!lin || (a->flags & LN_LINEAR_EXCLUDES)) return STZS_EINVAL;
     const int nk = a->ci_pad / 32, Z = a->splitk > 1 ? a->splitk : 1, nks = nk / Z;
     const bool split = Z > 1;
     if (a->B <= 0 || a->T_in <= 0 || a->Co <= 0 || a->Co > a->co_pad || a->co_pad % 128 || a->Ci > a->ci_pad ||
@@ -336,21 +339,16 @@ static int plain_launch(const stzs_conv_args* a, hipStream_t s) {
     if (!k) return STZS_EINVAL;
     dim3 grid((unsigned)((a->Co + 16 * wpg - 1) / (16 * wpg)), (unsigned)(((long)a->B * a->T_in + LR_ROWS - 1) / LR_ROWS),
               (unsigned)Z);
-    hipLaunchKernelGGL(reinterpret_cast<void (*)(stzs_conv_args)>(k), grid, dim3(64 * wpg), 0, s, *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(reinterpret_cast<void (*)(stzs_conv_args)>(k), grid, dim3(64 * wpg), 0, s, *a);
 }
 
 extern "C" int stzs_ln_linear(const stzs_conv_args* a, const stzs_rowln_args* ln, void* stream) {
     if (!a || !a->w || !a->y) return STZS_EINVAL;
     if (!ln) return plain_launch(a, reinterpret_cast<hipStream_t>(stream));
     if (!ln->x || ln->lens) return STZS_EINVAL;  // (the ragged mask is stzs_row_layernorm's only)
-    const bool lin = a->ks == 1 && a->stride == 1 && a->pad == 0 && a->ups == 0 && a->T_in == a->T_out &&
-                     a->pro_mode == STZS_PRO_NONE && a->pro_act == STZS_ACT_NONE && !a->stat_part && !a->x_scale &&
-                     !a->res && !a->gate && a->splitk <= 1;
-    if (!lin || (a->flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32 | STZS_CONV_W_X3 |
-                             STZS_CONV_W_FRAG32 | STZS_CONV_UPS_NOISE)))
-        return STZS_EINVAL;
+    // a plain linear without fused statistics or an fp8 row scale; no residual, row gate or K slices behind a LayerNorm
+    const bool lin = stzs_plain_linear(*a) && !a->stat_part && !a->x_scale && !a->res && !a->gate && a->splitk <= 1;
+    if (!lin || (a->flags & LN_LINEAR_EXCLUDES)) return STZS_EINVAL;
     if (a->B <= 0 || a->T_in <= 0 || a->Co <= 0 || a->Co > a->co_pad || a->co_pad % 128) return STZS_ESHAPE;
     // the linear's K is the LayerNorm's row: C = Ci = ci_pad, 4 / 8 / 16 K-steps
     const int C = ln->C, nk = C / 32;
@@ -371,7 +369,5 @@ extern "C" int stzs_ln_linear(const stzs_conv_args* a, const stzs_rowln_args* ln
     if (!k) return STZS_EINVAL;  // an epilogue activation this form does not instantiate
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 grid((unsigned)((a->Co + 63) / 64), (unsigned)((ln->R + LR_ROWS - 1) / LR_ROWS));
-    hipLaunchKernelGGL(reinterpret_cast<void (*)(stzs_conv_args, stzs_rowln_args)>(k), grid, dim3(NTHR), 0, s, *a, *ln);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(reinterpret_cast<void (*)(stzs_conv_args, stzs_rowln_args)>(k), grid, dim3(NTHR), 0, s, *a, *ln);
 }

@@ -367,10 +367,8 @@ __global__ __launch_bounds__(256) void lstm_state_reset(gu32* sync, gu64* gran) 
 extern "C" int stzs_lstm_state_reset(void* sync, void* xchg, void* stream) {
     if (!sync) return STZS_EINVAL;
     constexpr int n = 1024 > TAG_BYTES / 8 ? 1024 : TAG_BYTES / 8;
-    hipLaunchKernelGGL(lstm_state_reset, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    return stzs_launch(lstm_state_reset, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        (gu32*)sync, (gu64*)xchg);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 // utterances per group: 16 above 16 utterances (one MFMA row tile: the step's MFMA, h-load and cell work of a
@@ -433,9 +431,7 @@ static int lstm_launch(const stzs_lstm_args* a, const stzs_lstm_args* b, void* s
     case n: {                                                                                               \
         auto k = a->precise ? (gr == 32 ? lstm_xchg<n, true, 32> : gr == 16 ? lstm_xchg<n, true, 16> : lstm_xchg<n, true>) \
                             : (gr == 32 ? lstm_xchg<n, false, 32> : gr == 16 ? lstm_xchg<n, false, 16> : lstm_xchg<n, false>); \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, grid, dim3(512), lds, s, *a, b ? *b : *a, groups);                           \
-        break;                                                                                              \
+        return stzs_launch(k, grid, dim3(512), lds, s, *a, b ? *b : *a, groups);                           \
     }
         STZS_LSTM_CASE(1)
         STZS_LSTM_CASE(2)
@@ -444,8 +440,6 @@ static int lstm_launch(const stzs_lstm_args* a, const stzs_lstm_args* b, void* s
 #undef STZS_LSTM_CASE
         default: return STZS_ESHAPE;
     }
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_lstm(const stzs_lstm_args* a, void* stream) {

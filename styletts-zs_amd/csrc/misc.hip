@@ -115,69 +115,55 @@ inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
 extern "C" int stzs_dn_cond(const float* pool, const float* temb, void* c, int R, int D, void* stream) {
     if (!pool || !temb || !c) return STZS_EINVAL;
     if (R <= 0 || D <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(dn_cond_kernel<bf16_t>, dim3(nblk((long)R * D)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    return stzs_launch(dn_cond_kernel<bf16_t>, dim3(nblk((long)R * D)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        pool, temb, reinterpret_cast<bf16_t*>(c), R, D, 1);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_dn_cond_steps(const float* pool, const float* temb, void* c, int R, int D, int steps,
                                   void* stream) {
     if (!pool || !temb || !c) return STZS_EINVAL;
     if (R <= 0 || D <= 0 || steps <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(dn_cond_kernel<bf16_t>, dim3(nblk((long)R * D * steps)), dim3(256), 0,
+    return stzs_launch(dn_cond_kernel<bf16_t>, dim3(nblk((long)R * D * steps)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), pool, temb, reinterpret_cast<bf16_t*>(c), R, D, steps);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_dn_cond_steps_f32(const float* pool, const float* temb, float* c, int R, int D, int steps,
                                       void* stream) {
     if (!pool || !temb || !c) return STZS_EINVAL;
     if (R <= 0 || D <= 0 || steps <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(dn_cond_kernel<float>, dim3(nblk((long)R * D * steps)), dim3(256), 0,
+    return stzs_launch(dn_cond_kernel<float>, dim3(nblk((long)R * D * steps)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), pool, temb, c, R, D, steps);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_adaln_expand(const float* mod, const float* table, float* out, int R, int D, int nchunk,
                                  int nlayers, unsigned scale_mask, void* stream) {
     if (!mod || !out) return STZS_EINVAL;
     if (R <= 0 || D <= 0 || nchunk <= 0 || nchunk > 32 || nlayers <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(adaln_expand_kernel, dim3(nblk((long)nlayers * R * nchunk * D)), dim3(256), 0,
+    return stzs_launch(adaln_expand_kernel, dim3(nblk((long)nlayers * R * nchunk * D)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), mod, table, out, R, D, nchunk, nlayers, scale_mask);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_cfg_euler(float* x, const float* D, int B, int N, int cfg, float scale, float s0, float dsig,
                               void* stream) {
     if (!x || !D) return STZS_EINVAL;
     if (B <= 0 || N <= 0 || !(s0 > 0.f)) return STZS_ESHAPE;
-    hipLaunchKernelGGL(cfg_euler_kernel, dim3(nblk((long)B * N)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    return stzs_launch(cfg_euler_kernel, dim3(nblk((long)B * N)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        x, D, B, N, cfg, scale, s0, dsig);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_state_init(float* x, const float* eps, int B, int N, int cfg, float sigma, void* stream) {
     if (!x || !eps) return STZS_EINVAL;
     if (B <= 0 || N <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(state_init_kernel, dim3(nblk((long)B * N)), dim3(256), 0,
+    return stzs_launch(state_init_kernel, dim3(nblk((long)B * N)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), x, eps, B, N, cfg, sigma);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_mean_rows(const float* x, float* y, int B, int L, int64_t ldx, int64_t bsx, int c0, int C,
                               int64_t ldy, void* stream) {
     if (!x || !y) return STZS_EINVAL;
     if (B <= 0 || L <= 0 || C <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(mean_rows_kernel, dim3(nblk((long)B * C)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    return stzs_launch(mean_rows_kernel, dim3(nblk((long)B * C)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        x, y, B, L, (long)ldx, (long)bsx, c0, C, (long)ldy);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_copy2d(const stzs_copy_args* a, void* stream) {
@@ -186,37 +172,31 @@ extern "C" int stzs_copy2d(const stzs_copy_args* a, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 g(nblk((long)a->B * a->R * a->C));
     if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL((copy_kernel<float, float>), g, dim3(256), 0, s, *a);
+        return stzs_launch((copy_kernel<float, float>), g, dim3(256), 0, s, *a);
     else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16)
-        hipLaunchKernelGGL((copy_kernel<float, bf16_t>), g, dim3(256), 0, s, *a);
+        return stzs_launch((copy_kernel<float, bf16_t>), g, dim3(256), 0, s, *a);
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16)
-        hipLaunchKernelGGL((copy_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, *a);
+        return stzs_launch((copy_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, *a);
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL((copy_kernel<bf16_t, float>), g, dim3(256), 0, s, *a);
+        return stzs_launch((copy_kernel<bf16_t, float>), g, dim3(256), 0, s, *a);
     else
         return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_embed(const int32_t* tok, const float* emb, void* y, int B, int T, int D, int64_t ldy,
                           void* stream) {
     if (!tok || !emb || !y) return STZS_EINVAL;
     if (B <= 0 || T <= 0 || D <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(embed_kernel<bf16_t>, dim3(T, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tok, emb,
+    return stzs_launch(embed_kernel<bf16_t>, dim3(T, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tok, emb,
                        reinterpret_cast<bf16_t*>(y), B, T, D, (long)ldy);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_embed_f32(const int32_t* tok, const float* emb, float* y, int B, int T, int D, int64_t ldy,
                               void* stream) {
     if (!tok || !emb || !y) return STZS_EINVAL;
     if (B <= 0 || T <= 0 || D <= 0) return STZS_ESHAPE;
-    hipLaunchKernelGGL(embed_kernel<float>, dim3(T, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tok, emb,
+    return stzs_launch(embed_kernel<float>, dim3(T, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tok, emb,
                        y, B, T, D, (long)ldy);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_embed_lens(const int32_t* tok, const float* emb, void* y, const int32_t* lens, int B, int T,
@@ -225,15 +205,13 @@ extern "C" int stzs_embed_lens(const int32_t* tok, const float* emb, void* y, co
     if (B <= 0 || T <= 0 || D <= 0) return STZS_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (out_dtype == STZS_BF16)
-        hipLaunchKernelGGL(embed_lens_kernel<bf16_t>, dim3(T, B), dim3(256), 0, s, tok, emb,
+        return stzs_launch(embed_lens_kernel<bf16_t>, dim3(T, B), dim3(256), 0, s, tok, emb,
                            reinterpret_cast<bf16_t*>(y), lens, B, T, D, (long)ldy);
     else if (out_dtype == STZS_F32)
-        hipLaunchKernelGGL(embed_lens_kernel<float>, dim3(T, B), dim3(256), 0, s, tok, emb,
+        return stzs_launch(embed_lens_kernel<float>, dim3(T, B), dim3(256), 0, s, tok, emb,
                            reinterpret_cast<float*>(y), lens, B, T, D, (long)ldy);
     else
         return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
 }
 
 extern "C" int stzs_init(int device) {

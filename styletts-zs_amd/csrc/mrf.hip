@@ -538,6 +538,22 @@ __global__ __launch_bounds__(NTH, 2) void narrow_conv(const stzs_conv_args a) {
     }
 }
 
+// the mrf_conv instance of a launch with an NR-slot weight ring: the Snake (MRF) convs with a residual and / or an
+// accumulate input; LeakyReLU or no activation without an accumulate input (the AdaIN residual blocks of the decoder /
+// prosody predictor); nullptr otherwise
+template <int NR>
+void (*pick_mrf(const stzs_conv_args& a))(stzs_conv_args) {
+    const bool r = a.res != nullptr;
+    if (a.pro_act == STZS_ACT_SNAKE) {
+        if (r) return a.acc_in ? mrf_conv<STZS_ACT_SNAKE, true, true, NR> : mrf_conv<STZS_ACT_SNAKE, true, false, NR>;
+        return a.acc_in ? mrf_conv<STZS_ACT_SNAKE, false, true, NR> : mrf_conv<STZS_ACT_SNAKE, false, false, NR>;
+    }
+    if (a.acc_in) return nullptr;
+    if (a.pro_act == STZS_ACT_LEAKY) return r ? mrf_conv<STZS_ACT_LEAKY, true, false, NR> : mrf_conv<STZS_ACT_LEAKY, false, false, NR>;
+    if (a.pro_act == STZS_ACT_NONE) return r ? mrf_conv<STZS_ACT_NONE, true, false, NR> : mrf_conv<STZS_ACT_NONE, false, false, NR>;
+    return nullptr;
+}
+
 }  // namespace
 
 // internal entry used by stzs_conv1d for STZS_CONV_W_LANE16 weights
@@ -548,40 +564,14 @@ __attribute__((visibility("hidden"))) int stzs_mrf_conv_launch(const stzs_conv_a
         (a.ups && (a.acc_in || a.stat_part || a.res_tdiv != 1)) ||
         a.ldy % 8 || a.bsy % 8 || (a.res && (a.ldr % 8 || a.bsr % 8)) || (a.acc_in && (a.lda % 8 || a.bsa % 8)))
         return STZS_ESHAPE;
-    if (a.pro_act == STZS_ACT_SNAKE && !a.pro_alpha) return STZS_EINVAL;
     dim3 grid((unsigned)a.B * (unsigned)((a.T_out + BT - 1) / BT), a.co_pad / BCO);
     // a grid below the CU count (batch 1) gets the deep ring: one workgroup per CU anyway, more bytes in flight
     const bool deep = (long)grid.x * grid.y < stzs_cu_count();
     const size_t lds = (((size_t)rows_in * P + 15) & ~(size_t)15) + (deep ? 8 : NSL) * SLOT;
     if (lds > 160 * 1024) return STZS_ESHAPE;
-    void (*k)(stzs_conv_args) = nullptr;
-#define STZS_MRF_PICK(NR)                                                                                        \
-    if (a.pro_act == STZS_ACT_SNAKE) {                                                                           \
-        if (a.res && a.acc_in)                                                                                   \
-            k = mrf_conv<STZS_ACT_SNAKE, true, true, NR>;                                                        \
-        else if (a.res)                                                                                          \
-            k = mrf_conv<STZS_ACT_SNAKE, true, false, NR>;                                                       \
-        else if (a.acc_in)                                                                                       \
-            k = mrf_conv<STZS_ACT_SNAKE, false, true, NR>;                                                       \
-        else                                                                                                     \
-            k = mrf_conv<STZS_ACT_SNAKE, false, false, NR>;                                                      \
-    } else if (!a.acc_in) { /* the AdaIN residual blocks of the decoder / prosody predictor */                   \
-        if (a.pro_act == STZS_ACT_LEAKY)                                                                         \
-            k = a.res ? mrf_conv<STZS_ACT_LEAKY, true, false, NR> : mrf_conv<STZS_ACT_LEAKY, false, false, NR>;  \
-        else if (a.pro_act == STZS_ACT_NONE)                                                                     \
-            k = a.res ? mrf_conv<STZS_ACT_NONE, true, false, NR> : mrf_conv<STZS_ACT_NONE, false, false, NR>;    \
-    }
-    if (deep) {
-        STZS_MRF_PICK(8)
-    } else {
-        STZS_MRF_PICK(4)
-    }
-#undef STZS_MRF_PICK
+    void (*k)(stzs_conv_args) = deep ? pick_mrf<8>(a) : pick_mrf<4>(a);
     if (!k) return STZS_ESHAPE;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, dim3(NTH), lds, s, a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(k, grid, dim3(NTH), lds, s, a);
 }
 
 // internal entry used by stzs_conv1d for STZS_CONV_W_NARROW32 weights
@@ -594,8 +584,5 @@ __attribute__((visibility("hidden"))) int stzs_narrow_conv_launch(const stzs_con
         return STZS_ESHAPE;
     const size_t lds = (((size_t)rows_in * P + 15) & ~(size_t)15) + NSL * NSLOT_B;
     dim3 grid((unsigned)a.B * (unsigned)((a.T_out + NBT - 1) / NBT));
-    (void)hipFuncSetAttribute((const void*)narrow_conv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(narrow_conv, grid, dim3(NTH), lds, s, a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(narrow_conv, grid, dim3(NTH), lds, s, a);
 }

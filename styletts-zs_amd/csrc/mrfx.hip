@@ -616,8 +616,8 @@ void (*pick_form(const stzs_conv_args& a))(stzs_conv_args) {
 // the precise FLAT linear (ks 1): validated and launched by stzs_mrfx_conv_launch
 static int mrfx_lin_launch(const stzs_conv_args& a, hipStream_t s) {
     if (a.pad || a.stride != 1 || a.T_in != a.T_out || a.pro_mode != STZS_PRO_NONE || a.pro_act != STZS_ACT_NONE ||
-        a.stat_part || a.ups || a.refl || a.cic != 128 || a.ci_pad % 128 || a.Co % 8 || a.co_pad % BCO ||
-        a.in_dtype != STZS_F32 || a.out_dtype != STZS_F32 || a.ldx % 8 || a.bsx % 8 || a.ldy % 8 || a.bsy % 8 ||
+        a.stat_part || a.ups || a.refl || a.cic != 128 || a.ci_pad % 128 || a.Co % 8 ||
+        a.in_dtype != STZS_F32 || a.out_dtype != STZS_F32 || a.ldy % 8 || a.bsy % 8 ||
         (a.res && (a.ldr % 8 || a.bsr % 8 || a.res_tdiv != 1)) || (a.acc_in && (a.lda % 8 || a.bsa % 8)) ||
         (long)a.B * a.T_in >= (1L << 22) - 256 || (long)a.B * a.bsx >= (1L << 31))
         return STZS_ESHAPE;
@@ -627,22 +627,20 @@ static int mrfx_lin_launch(const stzs_conv_args& a, hipStream_t s) {
     void (*k)(stzs_conv_args) = pick_lin(a);
     if (!k) return STZS_EINVAL;
     const size_t lds = (size_t)2 * 128 * PX;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid((unsigned)(((long)a.B * a.T_in + 127) / 128), a.co_pad / BCO);
-    hipLaunchKernelGGL(k, grid, dim3(NTH), lds, s, a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(k, grid, dim3(NTH), lds, s, a);
 }
 
 // internal entry used by stzs_conv1d for STZS_CONV_W_FRAG32X3 weights (csrc/dispatch.hip)
 __attribute__((visibility("hidden"))) int stzs_mrfx_conv_launch(const stzs_conv_args& a, hipStream_t s) {
+    if (a.in_dtype == STZS_F8 || a.x_scale) return STZS_EDTYPE;
     if (a.ks == 1) return mrfx_lin_launch(a, s);
     // conv_post (128 -> 22, k7, LeakyReLU(0.01), fp32 out): the narrow form, waves split the rows
     const bool narrow = a.Co <= 32 && a.ci_pad == 128 && a.ks == 7 && !a.res && !a.acc_in && !a.stat_part &&
                         a.pro_mode == STZS_PRO_NONE && a.pro_act == STZS_ACT_LEAKY && a.alpha == 1.f &&
                         128 + 6 * a.dil <= 16 * sb_rows(7, 128);
-    if (a.stride != 1 || a.cic != 128 || a.ci_pad % 128 || (a.Co % 8 && !narrow) || a.co_pad % BCO || a.ups || a.refl || a.gate ||
-        a.in_dtype != STZS_F32 || a.out_dtype != STZS_F32 || a.epi_act != STZS_ACT_NONE || a.ldx % 8 || a.bsx % 8 ||
+    if (a.stride != 1 || a.cic != 128 || a.ci_pad % 128 || (a.Co % 8 && !narrow) || a.ups || a.refl || a.gate ||
+        a.in_dtype != STZS_F32 || a.out_dtype != STZS_F32 || a.epi_act != STZS_ACT_NONE ||
         a.ldy % 8 || a.bsy % 8 || (a.res && (a.ldr % 8 || a.bsr % 8 || a.res_tdiv <= 0)) ||
         (a.acc_in && (a.lda % 8 || a.bsa % 8)) || (a.stat_part && a.stat_ld < a.Co) ||
         (a.ks != 3 && a.ks != 7 && a.ks != 11))
@@ -650,7 +648,6 @@ __attribute__((visibility("hidden"))) int stzs_mrfx_conv_launch(const stzs_conv_
     if (!stzs_aligned(a.x, 32) || !stzs_aligned(a.y, 32) || (a.res && !stzs_aligned(a.res, 32)) ||
         (a.acc_in && !stzs_aligned(a.acc_in, 32)))
         return STZS_EINVAL;
-    if (a.pro_act == STZS_ACT_SNAKE && !a.pro_alpha) return STZS_EINVAL;
     if (a.pro_act == STZS_ACT_SNAKE && a.res && a.res_tdiv != 1) return STZS_ESHAPE;  // (TD1 in the kernel)
     const int ks = a.ks;
     // 128-row tiles while the hi + lo tile pair of the halo'd rows fits two workgroups per CU, else 64-row tiles
@@ -666,9 +663,6 @@ __attribute__((visibility("hidden"))) int stzs_mrfx_conv_launch(const stzs_conv_
     if (!k) return STZS_ESHAPE;
     const int rows_in = bt + (ks - 1) * a.dil;
     const size_t lds = (size_t)2 * rows_in * PX + NCS * 128 * 4;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid((unsigned)a.B * (unsigned)((a.T_out + bt - 1) / bt), narrow ? 1u : (unsigned)(a.co_pad / BCO));
-    hipLaunchKernelGGL(k, grid, dim3(NTH), lds, s, a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(k, grid, dim3(NTH), lds, s, a);
 }

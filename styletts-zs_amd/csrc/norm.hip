@@ -178,23 +178,16 @@ static int chan_stats_pass1(const stzs_stats_args* a, hipStream_t s, int* nchunk
     if (a->C % 8) return STZS_ESHAPE;
     const int nchunk = (a->T + STAT_ROWS - 1) / STAT_ROWS;
     dim3 g1(nchunk, a->B, (a->C + STAT_CG * 8 - 1) / (STAT_CG * 8));
-    if (a->dtype == STZS_BF16)
-        hipLaunchKernelGGL(chan_stats_partial<bf16_t>, g1, dim3(256), 0, s, *a, nchunk);
-    else if (a->dtype == STZS_F32)
-        hipLaunchKernelGGL(chan_stats_partial<float>, g1, dim3(256), 0, s, *a, nchunk);
-    else
-        return STZS_EDTYPE;
     *nchunk_out = nchunk;
-    return STZS_OK;
+    if (a->dtype == STZS_BF16) return stzs_launch(chan_stats_partial<bf16_t>, g1, dim3(256), 0, s, *a, nchunk);
+    if (a->dtype == STZS_F32) return stzs_launch(chan_stats_partial<float>, g1, dim3(256), 0, s, *a, nchunk);
+    return STZS_EDTYPE;
 }
 
 extern "C" int stzs_chan_stats_partial(const stzs_stats_args* a, void* stream) {
     if (!a || !a->x || !a->partial) return STZS_EINVAL;
     int nchunk = 0;
-    const int rc = chan_stats_pass1(a, reinterpret_cast<hipStream_t>(stream), &nchunk);
-    if (rc != STZS_OK) return rc;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return chan_stats_pass1(a, reinterpret_cast<hipStream_t>(stream), &nchunk);
 }
 
 extern "C" int stzs_chan_stats(const stzs_stats_args* a, void* stream) {
@@ -203,10 +196,7 @@ extern "C" int stzs_chan_stats(const stzs_stats_args* a, void* stream) {
     int nchunk = 0;
     const int rc = chan_stats_pass1(a, s, &nchunk);
     if (rc != STZS_OK) return rc;
-    STZS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(chan_stats_final, dim3(a->B, (a->C + FIN_CH - 1) / FIN_CH), dim3(256), 0, s, *a, nchunk);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(chan_stats_final, dim3(a->B, (a->C + FIN_CH - 1) / FIN_CH), dim3(256), 0, s, *a, nchunk);
 }
 
 extern "C" int stzs_chan_stats_final(const stzs_stats_args* a, int chunk_rows, void* stream) {
@@ -214,9 +204,7 @@ extern "C" int stzs_chan_stats_final(const stzs_stats_args* a, int chunk_rows, v
     if (a->B <= 0 || a->T <= 0 || a->C <= 0 || chunk_rows <= 0) return STZS_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int nchunk = (a->T + chunk_rows - 1) / chunk_rows;
-    hipLaunchKernelGGL(chan_stats_final, dim3(a->B, (a->C + FIN_CH - 1) / FIN_CH), dim3(256), 0, s, *a, nchunk);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(chan_stats_final, dim3(a->B, (a->C + FIN_CH - 1) / FIN_CH), dim3(256), 0, s, *a, nchunk);
 }
 
 extern "C" int stzs_chan_stats_final_group(const stzs_stats_args* a, int n, int chunk_rows, void* stream) {
@@ -232,9 +220,7 @@ extern "C" int stzs_chan_stats_final_group(const stzs_stats_args* a, int n, int 
         const int ny = (a[i].C + FIN_CH - 1) / FIN_CH;
         gy = ny > gy ? ny : gy;
     }
-    hipLaunchKernelGGL(chan_stats_final_group, dim3(gx, gy, n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(chan_stats_final_group, dim3(gx, gy, n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g);
 }
 
 extern "C" int stzs_row_layernorm(const stzs_rowln_args* a, void* stream) {
@@ -246,24 +232,16 @@ extern "C" int stzs_row_layernorm(const stzs_rowln_args* a, void* stream) {
     if (a->lens && (a->T <= 0 || a->R % a->T)) return STZS_ESHAPE;  // ragged mask: R = blocks of T rows
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 g((a->R + 3) / 4);
-    if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16)
-        hipLaunchKernelGGL((row_ln<bf16_t, bf16_t>), g, dim3(256), 0, s, *a);
-    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16)
-        hipLaunchKernelGGL((row_ln<float, bf16_t>), g, dim3(256), 0, s, *a);
-    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL((row_ln<float, float>), g, dim3(256), 0, s, *a);
-    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL((row_ln<bf16_t, float>), g, dim3(256), 0, s, *a);
-    else if (a->out_dtype == STZS_F8 && (!a->y_scale || a->ldy % 16))
-        return STZS_EINVAL;
-    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F8)
-        hipLaunchKernelGGL((row_ln<float, f8_t>), g, dim3(256), 0, s, *a);
-    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F8)
-        hipLaunchKernelGGL((row_ln<bf16_t, f8_t>), g, dim3(256), 0, s, *a);
-    else
-        return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    void (*k)(stzs_rowln_args) = nullptr;
+    if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16) k = row_ln<bf16_t, bf16_t>;
+    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16) k = row_ln<float, bf16_t>;
+    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32) k = row_ln<float, float>;
+    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32) k = row_ln<bf16_t, float>;
+    else if (a->out_dtype == STZS_F8 && (!a->y_scale || a->ldy % 16)) return STZS_EINVAL;
+    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F8) k = row_ln<float, f8_t>;
+    else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F8) k = row_ln<bf16_t, f8_t>;
+    else return STZS_EDTYPE;
+    return stzs_launch(k, g, dim3(256), 0, s, *a);
 }
 
 extern "C" int stzs_quant_rows(const stzs_quant_args* a, void* stream) {
@@ -271,7 +249,5 @@ extern "C" int stzs_quant_rows(const stzs_quant_args* a, void* stream) {
     if (a->R <= 0 || a->C <= 0 || a->C % 8 || a->C > 2048 || a->ldx % 8 || a->ldy % 16 || a->ldy < a->C)
         return STZS_ESHAPE;
     if (!stzs_aligned(a->x, 16) || !stzs_aligned(a->y, 16)) return STZS_EINVAL;
-    hipLaunchKernelGGL(quant_rows, dim3((a->R + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(quant_rows, dim3((a->R + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
 }

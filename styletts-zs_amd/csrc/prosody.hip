@@ -167,22 +167,16 @@ extern "C" int stzs_predictor_prep(const stzs_prprep_args* a, void* stream) {
     if (!a || !a->codes || !a->h || !a->y) return STZS_EINVAL;
     if (a->B <= 0 || a->T <= 0 || a->L <= 0 || a->Ch % 8 || a->ldh % 8 || a->ldy % 8) return STZS_ESHAPE;
     if (a->f32 > 1) return STZS_EINVAL;
-    if (a->f32)
-        hipLaunchKernelGGL(pr_prep<float>, dim3(a->T, a->B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
-    else
-        hipLaunchKernelGGL(pr_prep<bf16_t>, dim3(a->T, a->B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (a->f32) return stzs_launch(pr_prep<float>, dim3(a->T, a->B), dim3(256), 0, s, *a);
+    return stzs_launch(pr_prep<bf16_t>, dim3(a->T, a->B), dim3(256), 0, s, *a);
 }
 
 extern "C" int stzs_durations(const stzs_dur_args* a, void* stream) {
     if (!a || !a->logits || !a->dur) return STZS_EINVAL;
     if (a->B <= 0 || a->T <= 0 || a->nbins <= 0) return STZS_ESHAPE;
     const long n = (long)a->B * a->T;
-    hipLaunchKernelGGL(dur_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(dur_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
 }
 
 extern "C" int stzs_alignment(const stzs_align_args* a, void* stream) {
@@ -190,15 +184,9 @@ extern "C" int stzs_alignment(const stzs_align_args* a, void* stream) {
     if (a->B <= 0 || a->T <= 0 || a->T40 <= 0 || a->T > 16384) return STZS_ESHAPE;
     // T + 1 scan entries in dynamic LDS: 65 540 bytes at T = 16384.  The runtime's headers do not say whether a request
     // above 64 KiB needs the function attribute; lstm.hip's exchange kernels set it and run, so this launch does the
-    // same (T = 16384 is tested against the reference).  A refused attribute is an error, never a launch.
+    // same (stzs_launch; T = 16384 is tested against the reference).
     const size_t lds = (size_t)(a->T + 1) * sizeof(int);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return STZS_EHIP;
-    hipLaunchKernelGGL(align_kernel, dim3(a->B), dim3(256), lds,
-                       reinterpret_cast<hipStream_t>(stream), *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(align_kernel, dim3(a->B), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), *a);
 }
 
 extern "C" int stzs_gather_rows(const stzs_gather_args* a, void* stream) {
@@ -206,28 +194,18 @@ extern "C" int stzs_gather_rows(const stzs_gather_args* a, void* stream) {
     if (a->B <= 0 || a->Tdst <= 0 || a->C % 8 || a->xc0 % 8 || a->yc0 % 8 || a->ldx % 8 || a->ldy % 8)
         return STZS_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (a->dtype == STZS_BF16)
-        hipLaunchKernelGGL(gather_kernel<bf16_t>, dim3(a->Tdst, a->B), dim3(256), 0, s, *a);
-    else if (a->dtype == STZS_F32)
-        hipLaunchKernelGGL(gather_kernel<float>, dim3(a->Tdst, a->B), dim3(256), 0, s, *a);
-    else
-        return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    if (a->dtype == STZS_BF16) return stzs_launch(gather_kernel<bf16_t>, dim3(a->Tdst, a->B), dim3(256), 0, s, *a);
+    if (a->dtype == STZS_F32) return stzs_launch(gather_kernel<float>, dim3(a->Tdst, a->B), dim3(256), 0, s, *a);
+    return STZS_EDTYPE;
 }
 
 extern "C" int stzs_adain_dwup(const stzs_dwup_args* a, void* stream) {
     if (!a || !a->x || !a->y || !a->mean || !a->rstd || !a->gb || !a->w || !a->wb) return STZS_EINVAL;
     if (a->B <= 0 || a->T <= 0 || a->C <= 0) return STZS_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (a->dtype == STZS_BF16)
-        hipLaunchKernelGGL(dwup_kernel<bf16_t>, dim3(2 * a->T, a->B), dim3(256), 0, s, *a);
-    else if (a->dtype == STZS_F32)
-        hipLaunchKernelGGL(dwup_kernel<float>, dim3(2 * a->T, a->B), dim3(256), 0, s, *a);
-    else
-        return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    if (a->dtype == STZS_BF16) return stzs_launch(dwup_kernel<bf16_t>, dim3(2 * a->T, a->B), dim3(256), 0, s, *a);
+    if (a->dtype == STZS_F32) return stzs_launch(dwup_kernel<float>, dim3(2 * a->T, a->B), dim3(256), 0, s, *a);
+    return STZS_EDTYPE;
 }
 
 extern "C" int stzs_f0n_down(const stzs_f0n_args* a, void* stream) {
@@ -235,12 +213,8 @@ extern "C" int stzs_f0n_down(const stzs_f0n_args* a, void* stream) {
     if (a->B <= 0 || a->T80 <= 0 || a->T80 % 2) return STZS_ESHAPE;
     const long n = (long)a->B * (a->T80 / 2);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (a->dtype == STZS_BF16)
-        hipLaunchKernelGGL(f0n_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *a);
-    else if (a->dtype == STZS_F32)
-        hipLaunchKernelGGL(f0n_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *a);
-    else
-        return STZS_EDTYPE;
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    const dim3 g((unsigned)((n + 255) / 256));
+    if (a->dtype == STZS_BF16) return stzs_launch(f0n_kernel<bf16_t>, g, dim3(256), 0, s, *a);
+    if (a->dtype == STZS_F32) return stzs_launch(f0n_kernel<float>, g, dim3(256), 0, s, *a);
+    return STZS_EDTYPE;
 }

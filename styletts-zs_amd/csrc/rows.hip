@@ -19,7 +19,7 @@
 // The summation order of an output element -- sequential MFMA chain per wave, waves 0..3, then slices 0..Z-1 --
 // depends on K and Z only, never on the row count: results are batch-invariant (row blocks of up to 128 rows
 // tile larger M with identical per-element arithmetic).
-#include "common.hpp"
+#include "conv_args.hpp"
 
 namespace {
 
@@ -284,13 +284,10 @@ extern "C" size_t stzs_conv_rows_workspace(int64_t rows, int32_t Co, int32_t kgr
     return rows_form > r16 ? rows_form : r16;
 }
 
-// validates the linear and launches
+// internal entry used by stzs_conv1d for STZS_CONV_ROWS (csrc/dispatch.hip): this form's own conditions, and launches
 int stzs_rows_gemm_launch(const stzs_conv_args& a, hipStream_t s) {
-    const bool lin = a.ks == 1 && a.stride == 1 && a.pad == 0 && a.ups == 0 && a.T_in == a.T_out &&
-                     a.pro_mode == STZS_PRO_NONE && a.pro_act == STZS_ACT_NONE && !a.stat_part && !a.x_scale;
-    if (!lin || (a.flags & (STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32 | STZS_CONV_W_X3 |
-                            STZS_CONV_W_FRAG32)))
-        return STZS_EINVAL;
+    // a plain linear without fused statistics or an fp8 row scale
+    if (!stzs_plain_linear(a) || a.stat_part || a.x_scale) return STZS_EINVAL;
     if (a.in_dtype == STZS_F8) return STZS_EDTYPE;
     if (a.in_dtype == STZS_BF16 ? a.pro_cscale != 1.f : false) return STZS_EINVAL;
     if (a.res && a.res_tdiv != 1) return STZS_EINVAL;  // gemm_rows reads the residual at the output row itself
@@ -313,7 +310,5 @@ int stzs_rows_gemm_launch(const stzs_conv_args& a, hipStream_t s) {
     else if (a.in_dtype == STZS_F32 && a.out_dtype == STZS_F32) k = pick<float, float>(mt, kpw, split, a.epi_act);
     else return STZS_EDTYPE;
     if (!k) return STZS_EINVAL;  // an epilogue activation this form does not instantiate
-    hipLaunchKernelGGL(reinterpret_cast<void (*)(stzs_conv_args)>(k), grid, dim3(NTHR), 0, s, a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(reinterpret_cast<void (*)(stzs_conv_args)>(k), grid, dim3(NTHR), 0, s, a);
 }

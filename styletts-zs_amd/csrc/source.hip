@@ -248,15 +248,10 @@ extern "C" int stzs_harmonic_source(const stzs_source_args* a, void* stream) {
     if (a->hop <= 0 || (NS - 2) / a->hop + 2 > KW) return STZS_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n = a->B * a->nh;
-    hipLaunchKernelGGL(phase_prefix_kernel, dim3(n), dim3(256), 0, s, *a);
-    STZS_LAUNCH_CHECK();
+    if (const int rc = stzs_launch(phase_prefix_kernel, dim3(n), dim3(256), 0, s, *a)) return rc;
     const int N = a->T80 * a->hop;
     const int Tf = N / a->hop_s + 1;
     const size_t lds = (size_t)(NS + 3 * a->n_fft) * 4 + (size_t)a->nh * (8 + 4 + 2 * KW * 4);
-    if (a->n_fft == 20)
-        hipLaunchKernelGGL(source_stft_kernel<20>, dim3((Tf + FB - 1) / FB, a->B), dim3(256), lds, s, *a);
-    else
-        hipLaunchKernelGGL(source_stft_kernel<0>, dim3((Tf + FB - 1) / FB, a->B), dim3(256), lds, s, *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(a->n_fft == 20 ? source_stft_kernel<20> : source_stft_kernel<0>, dim3((Tf + FB - 1) / FB, a->B),
+                       dim3(256), lds, s, *a);
 }

@@ -169,9 +169,7 @@ extern "C" int stzs_stft_logmel(const stzs_stftmel_args* a, void* stream) {
     const size_t lds = ((size_t)4 * M + M + 1) * sizeof(float);  // <= 40 KB + 4 B at n_fft 4096
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a->out_dtype == STZS_F32)
-        hipLaunchKernelGGL(stft_logmel_kernel<float>, dim3(a->F, a->B), dim3(FT), lds, s, *a);
+        return stzs_launch(stft_logmel_kernel<float>, dim3(a->F, a->B), dim3(FT), lds, s, *a);
     else
-        hipLaunchKernelGGL(stft_logmel_kernel<bf16_t>, dim3(a->F, a->B), dim3(FT), lds, s, *a);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+        return stzs_launch(stft_logmel_kernel<bf16_t>, dim3(a->F, a->B), dim3(FT), lds, s, *a);
 }

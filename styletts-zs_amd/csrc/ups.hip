@@ -272,8 +272,5 @@ __attribute__((visibility("hidden"))) int stzs_ups_conv_launch(const stzs_conv_a
         default: return STZS_ESHAPE;
     }
 #undef STZS_UPS_PICK
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)nqt, (unsigned)groups), dim3(NTH), lds, s, a, ctw);
-    STZS_LAUNCH_CHECK();
-    return STZS_OK;
+    return stzs_launch(k, dim3((unsigned)nqt, (unsigned)groups), dim3(NTH), lds, s, a, ctw);
 }

@@ -1,0 +1,82 @@
+"""The native dispatch, checked without a device (tools/dispatch_trace.py): the library's objects linked against the
+recording runtime stand-in (tools/hip_record/hip_record.cpp) run their real validation and routing on fake pointers,
+and every launch is recorded.  Properties only -- no golden digest: a routing rule changed on purpose needs no edit
+here.  The trace library is linked into a temporary directory and loaded by child processes only."""
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+TOOL = os.path.join(ROOT, "tools", "dispatch_trace.py")
+OBJECTS = os.path.join(ROOT, "styletts-zs_amd", "build")
+LDS_MAX = 160 * 1024
+
+pytestmark = pytest.mark.skipif(
+    shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime.h") or
+    not os.path.exists(os.path.join(OBJECTS, "dispatch.o")),
+    reason="needs g++, the HIP headers and the library's objects (styletts-zs_amd/build.py)")
+
+
+def _run(tmp, *args):
+    r = subprocess.run([sys.executable, TOOL, "--lib", str(tmp / "libstzs_trace.so")] + [str(a) for a in args],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout
+
+
+@pytest.fixture(scope="module")
+def sweeps(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("dispatch_trace")
+    for n in ("a", "b"):
+        _run(tmp, "--sweep", "--out", tmp / f"sweep_{n}.txt")
+    return tmp / "sweep_a.txt", tmp / "sweep_b.txt"
+
+
+def test_sweep_accepted_calls_launch_rejected_calls_do_not(sweeps):
+    """every accepted call launches (non-zero grid and block, LDS within the CU's 160 KB); a rejected stzs_conv1d /
+    stzs_ln_linear call makes no runtime call at all -- stzs.h's "validates before any HIP call" over the whole
+    sweep; a rejected group has launched at most the problems before the failing one (two kernels each at most)"""
+    import dispatch_trace as D
+    entries = D.parse(sweeps[0])
+    assert len(entries) > 5000
+    accepted = rejected = 0
+    for kind, label, rc, lines in entries:
+        assert kind == "call" and rc is not None, label
+        if rc < 0:
+            rejected += 1
+            # (stzs_conv1d_group returns the first failing problem's code: "the problems before it have been launched")
+            if label.startswith("stzs_conv1d_group"):
+                assert sum(ln.startswith("L ") for ln in lines) <= 2 * 2, (label, rc, lines)
+            else:
+                assert not lines, (label, rc, lines[:3])
+            continue
+        accepted += 1
+        launches = [ln.split() for ln in lines if ln.startswith("L ")]
+        assert launches, (label, rc)
+        for ln in launches:
+            assert ln[1] != "?", (label, ln)  # (a registered kernel)
+            assert all(int(v) > 0 for v in ln[2:8]) and 0 <= int(ln[8]) <= LDS_MAX, (label, ln)
+        for ln in lines:
+            if ln.startswith("A "):
+                assert 0 < int(ln.split()[3]) <= LDS_MAX, (label, ln)
+    assert accepted > 1000 and rejected > 1000, (accepted, rejected)
+
+
+def test_sweep_deterministic(sweeps):
+    assert open(sweeps[0]).read() == open(sweeps[1]).read()
+
+
+def test_synth_trace_matches_engine_launch_count(tmp_path):
+    """the eight cases at the tiny spec through the real dispatch: the engine's launch count is the number of library
+    calls that launched (a group call counting as its return value), and no case launches fewer kernels than that"""
+    out = _run(tmp_path, "--synth", "tiny", "--out", tmp_path / "synth.txt")
+    rows = [dict(f.split("=") for f in ln.split()[1:]) for ln in out.splitlines() if "engine.launches=" in ln]
+    assert len(rows) == 8, out
+    for r in rows:
+        assert int(r["engine.launches"]) == int(r["launching_calls"]) > 0, r
+        assert int(r["kernels"]) >= int(r["launching_calls"]), r
+    assert "L ? " not in open(tmp_path / "synth.txt").read()

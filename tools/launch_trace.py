@@ -92,12 +92,16 @@ class RecordingLib:
 
 
 class _Patched:
-    """the stub in place of stzs._lib.load, and a null stream for every engine, while the cases run"""
+    """the stub in place of stzs._lib.load (unless record is false: tools/dispatch_trace.py keeps the real load, of a
+    library linked against a recording runtime), and a null stream for every engine, while the cases run"""
+
+    def __init__(self, record=True):
+        self.lib = RecordingLib() if record else None
 
     def __enter__(self):
-        self.lib = RecordingLib()
         self.saved = (_lib.load, engine.StyleTTSZS.stream, torch.from_numpy)
-        _lib.load = lambda: self.lib
+        if self.lib:
+            _lib.load = lambda: self.lib
         engine.StyleTTSZS.stream = lambda eng: C.c_void_p(0)
         # on "cpu" an uploaded host constant would alias its numpy array, whose alignment varies from run to run (the
         # engine routes on 16- and 32-byte alignment); a copy gives it torch's 64-byte alignment, as a device upload
@@ -109,12 +113,13 @@ class _Patched:
         _lib.load, engine.StyleTTSZS.stream, torch.from_numpy = self.saved
 
 
-def run_cases(spec_name="tiny"):
-    """-> [(case name, [call, ...], engine.launches)] of the eight cases on fresh engines"""
+def run_cases(spec_name="tiny", record=True, on_case=None):
+    """-> [(case name, [call, ...], engine.launches)] of the eight cases on fresh engines; record = False keeps the
+    real stzs._lib.load (no calls recorded), on_case(name) is called before each case's synthesis"""
     S = {"tiny": SPEC_TINY, "v0": SPEC_V0}[spec_name]
     P = init_params(S, 0)
     out = []
-    with _Patched() as lib:
+    with _Patched(record) as lib:
         mk = lambda **kw: engine.StyleTTSZS(S, P, device="cpu", **kw)
         bf16, pf8 = mk(), mk(precise=True, fp8_denoiser=True)
         lat = engine.StyleTTSZS(S, None, device="cpu", packed=bf16.W, dn_splitk=engine.LATENCY_DN_SPLITK,
@@ -129,14 +134,17 @@ def run_cases(spec_name="tiny"):
             tok, ref, eps, dur = make_inputs(S, B, 7)
             kw = dict(steps=steps, cfg_scale=CFG, noise=eps, durations=dur, seeds=list(range(B)),
                       n_frames=int(dur.sum(1).max()), check=False)
-            del lib.calls[:]
+            calls = lib.calls if lib else []
+            del calls[:]
+            if on_case:
+                on_case(name)
             if stream is None:
                 eng.synth(tok, ref, **kw)
             else:
                 for _ in eng.synth_stream(tok, ref, **kw, **stream):
                     pass
             # (last record: the buffer / scratch keys in the order they were first requested)
-            out.append((name, lib.calls + [["buffers"] + [str(k) for k in eng._bufs]], eng.launches))
+            out.append((name, calls + [["buffers"] + [str(k) for k in eng._bufs]], eng.launches))
     return out
 
 
