@@ -515,6 +515,15 @@ typedef struct stzs_frames_args {
     void* y;               /* [B, F, ldy] bf16, F = N / hop + 1 */
     int64_t ldw, ldy, bsy;
     int32_t B, N, F, n_fft, win, hop;
+    /* ragged reference batch (optional int32 [B] in SAMPLES, NULL = N samples everywhere, the launch as before):
+     * utterance b holds N_b = n_lens[b] samples, clamped into [n_fft / 2 + 1, N]; the reflect padding mirrors at its
+     * own last sample N_b - 1, and samples at or past N_b are never read.  Frames t < F_b = N_b / hop + 1 are then the
+     * bits of a launch of that utterance alone with N = N_b; rows t >= F_b are stored as zeros over all ldy columns. */
+    const int32_t* n_lens;
+    /* optional int32 [B] OUTPUT, honoured with n_lens only (set without it: STZS_EINVAL): f_lens_out[b] = F_b, written
+     * by the frame-0 workgroup of utterance b -- the row counts later launches on the same stream take as their
+     * `lens`, so lengths that live on the device need no host arithmetic and no sync */
+    int32_t* f_lens_out;
 } stzs_frames_args;
 int stzs_stft_frames(const stzs_frames_args* a, void* stream);
 /* y[b, t, m] = log(max(sum_{k0 <= k < k1} fb[m][k] (re_k^2 + im_k^2), 1e-5)), [k0, k1) = ranges[m] */
@@ -525,6 +534,10 @@ typedef struct stzs_logmel_args {
     void* y;               /* [B, F, ldy] bf16 | f32 */
     int64_t lds, bss, ldy, bsy;
     int32_t B, F, nbin, n_mels, out_dtype, pad_i;
+    /* ragged batch (optional int32 [B] in ROWS, NULL = F rows everywhere): y[b, t, :n_mels] = 0 for
+     * t >= lens[b] (clamped into [1, F]) -- the zero padding a following conv sees at the end of a sequence of
+     * lens[b] frames -- and the spec rows of those frames are not read */
+    const int32_t* lens;
 } stzs_logmel_args;
 int stzs_log_mel(const stzs_logmel_args* a, void* stream);
 /* adaptive average pooling over time: y[b, i, c] = mean_{floor(iT/L) <= t < ceil((i+1)T/L)} x[b, t, c] */
@@ -533,8 +546,26 @@ typedef struct stzs_pool_args {
     void* y;
     int64_t ldx, bsx, ldy, bsy;
     int32_t B, T, L, C, in_dtype, out_dtype;
+    /* ragged batch (optional int32 [B] in ROWS, NULL = T rows everywhere): utterance b is pooled over its first
+     * T_b = lens[b] rows (clamped into [1, T]), y[b, i, c] = mean_{floor(i T_b / L) <= t < ceil((i+1) T_b / L)} -- the
+     * bits of that utterance alone at T = T_b; T_b < L is legal (overlapping windows, as torch); rows t >= T_b are
+     * not read */
+    const int32_t* lens;
 } stzs_pool_args;
 int stzs_pool_rows(const stzs_pool_args* a, void* stream);
+/* in place: x[b, t, c] = 0 for t >= lens[b] (clamped into [1, T]), c < C, exact zeros; rows below stay untouched.  The
+ * row mask between two convs of a ragged batch: what an activation leaves in a padding row (act(bias)) must be the
+ * zero padding the next conv would see at the end of a sequence of lens[b] rows.  16-byte stores where base, ld, bs
+ * and C allow them (all multiples of 16 bytes), element-wide vector stores otherwise.  lens is required (NULL:
+ * STZS_EINVAL); B, T, C <= 0, B > 65535, ld < C or bs < (T - 1) * ld + C: STZS_ESHAPE; dtype other than STZS_BF16 /
+ * STZS_F32: STZS_EDTYPE. */
+typedef struct stzs_mask_args {
+    void* x;               /* [B, T, ld] bf16 | f32 */
+    const int32_t* lens;   /* int32 [B] rows */
+    int64_t ld, bs;
+    int32_t B, T, C, dtype;
+} stzs_mask_args;
+int stzs_mask_rows(const stzs_mask_args* a, void* stream);
 /* the PRECISE log-mel in one launch (csrc/stftmel.hip; StyleTTSZS(precise_frontend=True)): per (utterance b, frame t)
  * one workgroup builds the frame of stzs_stft_frames in fp32 in LDS -- window[m] * x[reflect(t * hop + (n_fft - win) / 2
  * + m - n_fft / 2)] for m < win, centred in n_fft, zeros around it -- runs an n_fft-point real FFT on it in fp32 (an
@@ -556,6 +587,13 @@ typedef struct stzs_stftmel_args {
     void* y;               /* [B, F, ldy] bf16 | f32 */
     int64_t ldw, ldy, bsy;
     int32_t B, N, F, n_fft, win, hop, n_mels, out_dtype;
+    /* ragged reference batch, as stzs_stft_frames (both optional; NULL n_lens = the launch as before): n_lens int32
+     * [B] in samples, N_b = n_lens[b] clamped into [n_fft / 2 + 1, N], reflection at N_b - 1, nothing read at or past
+     * N_b; frames t < F_b = N_b / hop + 1 are the bits of utterance b alone at N = N_b, rows t >= F_b are stored as
+     * zeros (y[b, t, :n_mels]) by workgroups that leave before their first barrier.  f_lens_out int32 [B] output
+     * (with n_lens only, else STZS_EINVAL): F_b, written by the frame-0 workgroup of utterance b. */
+    const int32_t* n_lens;
+    int32_t* f_lens_out;
 } stzs_stftmel_args;
 int stzs_stft_logmel(const stzs_stftmel_args* a, void* stream);
 

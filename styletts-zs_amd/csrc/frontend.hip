@@ -9,6 +9,8 @@
 //                      (stzs/weights.py dft_basis), fp32 out;
 //   stzs_log_mel     : |X|^2 of the (re | im) rows, sparse mel filterbank (per-bin [k0, k1) ranges), log;
 //   stzs_pool_rows   : adaptive average pooling over time (torch.nn.functional.adaptive_avg_pool1d bounds);
+//   stzs_mask_rows   : a ragged reference batch's row mask between the two prompt convs (the frames, log-mel and pool
+//                      kernels take the per-utterance lengths themselves);
 //   stzs_code_quantize: the discrete style codes (README.md:5) -- product VQ of the projected prompt rows.
 #include "common.hpp"
 
@@ -19,21 +21,63 @@ __global__ __launch_bounds__(256) void frames_kernel(const stzs_frames_args a) {
     const float* X = a.wav + (long)b * a.ldw;
     bf16_t* Y = reinterpret_cast<bf16_t*>(a.y) + (long)b * a.bsy + (long)t * a.ldy;
     const int off = (a.n_fft - a.win) / 2;  // window centred in the n_fft frame
+    // ragged batch: the utterance's own sample count (clamped into the range the reflection is defined on) bounds the
+    // reflection; a frame past its last one is a row of zeros and reads no sample
+    int N = a.N;
+    if (a.n_lens) {
+        N = min(max(a.n_lens[b], a.n_fft / 2 + 1), a.N);
+        const int Fb = N / a.hop + 1;
+        if (t == 0 && threadIdx.x == 0 && a.f_lens_out) a.f_lens_out[b] = Fb;
+        if (t >= Fb) {
+            for (int m = threadIdx.x; m < a.ldy; m += 256) Y[m] = 0;
+            return;
+        }
+    }
     for (int m = threadIdx.x; m < a.ldy; m += 256) {
         float v = 0.f;
         if (m < a.win) {
             long j = (long)t * a.hop + off + m - a.n_fft / 2;  // sample index before reflect padding
             if (j < 0) j = -j;
-            if (j >= a.N) j = 2L * (a.N - 1) - j;
+            if (j >= N) j = 2L * (N - 1) - j;
             v = a.window[m] * X[j];
         }
         Y[m] = f2bf(v);
     }
 }
 
+// rows t >= clamp(lens[b], 1, T) of utterance b, as exact zeros: R rows per workgroup, V-byte stores (V = 16 where the
+// host found base, ld, bs and C multiples of 16 bytes, else one element)
+constexpr int MASK_ROWS = 16;
+template <typename V>
+__global__ __launch_bounds__(256) void mask_rows_kernel(const stzs_mask_args a, int esz) {
+    const int b = blockIdx.y, t0 = blockIdx.x * MASK_ROWS;
+    const int Tb = min(max(a.lens[b], 1), a.T);
+    const int r0 = max(t0, Tb), r1 = min(t0 + MASK_ROWS, a.T);
+    if (r0 >= r1) return;
+    const int per = (int)sizeof(V) / esz;  // elements per store
+    const int nv = a.C / per;              // (C is a whole number of them: checked on the host)
+    char* X = reinterpret_cast<char*>(a.x) + ((long)b * a.bs + (long)r0 * a.ld) * esz;
+    V z;
+    __builtin_memset(&z, 0, sizeof(V));
+    for (int i = threadIdx.x; i < (r1 - r0) * nv; i += 256) {
+        const int r = i / nv, c = i - r * nv;
+        *reinterpret_cast<V*>(X + (long)r * a.ld * esz + (long)c * sizeof(V)) = z;
+    }
+}
+
 __global__ __launch_bounds__(256) void log_mel_kernel(const stzs_logmel_args a) {
     extern __shared__ float pw[];
     const long r = (long)blockIdx.y * a.F + blockIdx.x;  // b * F + t
+    if (a.lens && (int)blockIdx.x >= min(max(a.lens[blockIdx.y], 1), a.F)) {
+        // ragged batch: a frame past the utterance's last one is stored as zeros, its spec row is not read (the whole
+        // workgroup takes this branch, before the barrier)
+        const long o = (long)blockIdx.y * a.bsy + (long)blockIdx.x * a.ldy;
+        for (int m = threadIdx.x; m < a.n_mels; m += 256) {
+            if (a.out_dtype == STZS_BF16) reinterpret_cast<bf16_t*>(a.y)[o + m] = 0;
+            else reinterpret_cast<float*>(a.y)[o + m] = 0.f;
+        }
+        return;
+    }
     const float* S = a.spec + (long)blockIdx.y * a.bss + (long)blockIdx.x * a.lds;
     for (int k = threadIdx.x; k < a.nbin; k += 256) {
         const float re = S[k], im = S[a.nbin + k];
@@ -56,8 +100,10 @@ __global__ __launch_bounds__(256) void log_mel_kernel(const stzs_logmel_args a) 
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void pool_kernel(const stzs_pool_args a) {
     const int i = blockIdx.x, b = blockIdx.y;
-    const int s = (int)(((long)i * a.T) / a.L);
-    const int e = (int)(((long)(i + 1) * a.T + a.L - 1) / a.L);
+    // ragged batch: the utterance's own row count; T < L gives overlapping windows of >= 1 row (s < e always: T >= 1)
+    const int T = a.lens ? min(max(a.lens[b], 1), a.T) : a.T;
+    const int s = (int)(((long)i * T) / a.L);
+    const int e = (int)(((long)(i + 1) * T + a.L - 1) / a.L);
     const TI* X = reinterpret_cast<const TI*>(a.x) + (long)b * a.bsx;
     TO* Y = reinterpret_cast<TO*>(a.y) + (long)b * a.bsy + (long)i * a.ldy;
     const float inv = 1.f / (float)(e - s);
@@ -157,6 +203,7 @@ extern "C" int stzs_code_quantize(const stzs_vq_args* a, void* stream) {
 
 extern "C" int stzs_stft_frames(const stzs_frames_args* a, void* stream) {
     if (!a || !a->wav || !a->window || !a->y) return STZS_EINVAL;
+    if (a->f_lens_out && !a->n_lens) return STZS_EINVAL;  // the frame counts are those of the ragged launch only
     if (a->B <= 0 || a->N < 2 || a->F <= 0 || a->hop <= 0 || a->win <= 0 || a->win > a->n_fft || a->ldy < a->win ||
         a->ldy % 8 || a->n_fft / 2 >= a->N)
         return STZS_ESHAPE;  // reflect padding needs N > n_fft / 2 (as torch)
@@ -172,6 +219,21 @@ extern "C" int stzs_log_mel(const stzs_logmel_args* a, void* stream) {
     if (a->out_dtype != STZS_BF16 && a->out_dtype != STZS_F32) return STZS_EDTYPE;
     return stzs_launch(log_mel_kernel, dim3(a->F, a->B), dim3(256), (size_t)a->nbin * 4,
                        reinterpret_cast<hipStream_t>(stream), *a);
+}
+
+extern "C" int stzs_mask_rows(const stzs_mask_args* a, void* stream) {
+    if (!a || !a->x || !a->lens) return STZS_EINVAL;
+    if (a->B <= 0 || a->B > 65535 || a->T <= 0 || a->C <= 0 || a->ld < a->C || a->bs < (int64_t)(a->T - 1) * a->ld + a->C)
+        return STZS_ESHAPE;
+    if (a->dtype != STZS_BF16 && a->dtype != STZS_F32) return STZS_EDTYPE;
+    const int esz = a->dtype == STZS_BF16 ? 2 : 4;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dim3 g((a->T + MASK_ROWS - 1) / MASK_ROWS, a->B);
+    const bool wide = reinterpret_cast<uintptr_t>(a->x) % 16 == 0 && (a->ld * esz) % 16 == 0 && (a->bs * esz) % 16 == 0 &&
+                      ((int64_t)a->C * esz) % 16 == 0;
+    if (wide) return stzs_launch(mask_rows_kernel<uint4>, g, dim3(256), 0, s, *a, esz);
+    if (esz == 2) return stzs_launch(mask_rows_kernel<uint16_t>, g, dim3(256), 0, s, *a, esz);
+    return stzs_launch(mask_rows_kernel<uint32_t>, g, dim3(256), 0, s, *a, esz);
 }
 
 extern "C" int stzs_pool_rows(const stzs_pool_args* a, void* stream) {

@@ -49,6 +49,21 @@ __global__ __launch_bounds__(FT) void stft_logmel_kernel(const stzs_stftmel_args
     float* pw = sm + 4 * M;
     const float2* tw = reinterpret_cast<const float2*>(a.twiddle);
 
+    // ragged batch: this utterance's own sample count, clamped into the range the reflection is defined on; a frame
+    // past its last one is a row of zeros (the padding the prompt convs see) and its workgroup leaves here -- t and b
+    // are the workgroup's, so the whole workgroup leaves, before any barrier
+    int N = a.N;
+    if (a.n_lens) {
+        N = min(max(a.n_lens[b], M + 1), a.N);
+        const int Fb = N / a.hop + 1;
+        if (t == 0 && tid == 0 && a.f_lens_out) a.f_lens_out[b] = Fb;
+        if (t >= Fb) {
+            TO* Z = reinterpret_cast<TO*>(a.y) + (long)b * a.bsy + (long)t * a.ldy;
+            for (int m = tid; m < a.n_mels; m += FT) DT<TO>::st(Z + m, 0.f);
+            return;
+        }
+    }
+
     // the frame as stzs_stft_frames defines it: torch.stft(center=True, pad_mode="reflect"), the window centred in n_fft
     // (the final clamp only keeps a frame count beyond N / hop + 1 inside the row)
     const float* X = a.wav + (long)b * a.ldw;
@@ -59,8 +74,8 @@ __global__ __launch_bounds__(FT) void stft_logmel_kernel(const stzs_stftmel_args
         if (mw >= 0 && mw < a.win) {
             long j = (long)t * a.hop + m - n_fft / 2;
             if (j < 0) j = -j;
-            if (j >= a.N) j = 2L * (a.N - 1) - j;
-            j = j < 0 ? 0 : (j >= a.N ? a.N - 1 : j);
+            if (j >= N) j = 2L * (N - 1) - j;
+            j = j < 0 ? 0 : (j >= N ? N - 1 : j);
             v = a.window[mw] * X[j];
         }
         ((m & 1) ? si : sr)[fswz(m >> 1)] = v;
@@ -157,6 +172,7 @@ __global__ __launch_bounds__(FT) void stft_logmel_kernel(const stzs_stftmel_args
 
 extern "C" int stzs_stft_logmel(const stzs_stftmel_args* a, void* stream) {
     if (!a || !a->wav || !a->window || !a->twiddle || !a->fb || !a->ranges || !a->y) return STZS_EINVAL;
+    if (a->f_lens_out && !a->n_lens) return STZS_EINVAL;  // the frame counts are those of the ragged launch only
     if (a->B <= 0 || a->B > 65535 || a->N <= 0 || a->F <= 0 || a->n_fft <= 0 || a->win <= 0 || a->hop <= 0 ||
         a->n_mels <= 0)
         return STZS_ESHAPE;

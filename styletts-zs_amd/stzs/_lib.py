@@ -139,26 +139,42 @@ class IstftStreamArgs(C.Structure):
                 ("B", i32), ("f0", i32), ("Fc", i32), ("final_chunk", i32), ("n_fft", i32), ("hop_s", i32)]
 
 
+class opt_vp(C.c_void_p):
+    """an OPTIONAL pointer field (NULL = the call as it was before the field existed): the same 8 bytes as a
+    c_void_p, assigned like one (an address or None; read back through .value), kept apart by its type -- a loop
+    over a struct's required pointers (tests/test_precise_frontend_host.py) does not take it for one, and
+    tools/launch_trace.py records it only when it is set, so a trace of calls that leave it NULL is the trace from
+    before the field.  The ragged-reference fields are declared with it."""
+
+
 class FramesArgs(C.Structure):
     _fields_ = [("wav", vp), ("window", vp), ("y", vp), ("ldw", i64), ("ldy", i64), ("bsy", i64)] + \
-               [(n, i32) for n in ("B", "N", "F", "n_fft", "win", "hop")]
+               [(n, i32) for n in ("B", "N", "F", "n_fft", "win", "hop")] + \
+               [("n_lens", opt_vp), ("f_lens_out", opt_vp)]  # ragged batch: samples per utterance in, frames out
 
 
 class LogMelArgs(C.Structure):
     _fields_ = [("spec", vp), ("fb", vp), ("ranges", vp), ("y", vp)] + \
                [(n, i64) for n in ("lds", "bss", "ldy", "bsy")] + \
-               [(n, i32) for n in ("B", "F", "nbin", "n_mels", "out_dtype", "pad_i")]
+               [(n, i32) for n in ("B", "F", "nbin", "n_mels", "out_dtype", "pad_i")] + \
+               [("lens", opt_vp)]  # optional int32 [B]: frames per utterance
 
 
 class StftMelArgs(C.Structure):
     _fields_ = [(n, vp) for n in ("wav", "window", "twiddle", "fb", "ranges", "y")] + \
                [(n, i64) for n in ("ldw", "ldy", "bsy")] + \
-               [(n, i32) for n in ("B", "N", "F", "n_fft", "win", "hop", "n_mels", "out_dtype")]
+               [(n, i32) for n in ("B", "N", "F", "n_fft", "win", "hop", "n_mels", "out_dtype")] + \
+               [("n_lens", opt_vp), ("f_lens_out", opt_vp)]  # ragged batch, as FramesArgs
 
 
 class PoolArgs(C.Structure):
     _fields_ = [("x", vp), ("y", vp)] + [(n, i64) for n in ("ldx", "bsx", "ldy", "bsy")] + \
-               [(n, i32) for n in ("B", "T", "L", "C", "in_dtype", "out_dtype")]
+               [(n, i32) for n in ("B", "T", "L", "C", "in_dtype", "out_dtype")] + \
+               [("lens", opt_vp)]  # optional int32 [B]: rows per utterance
+
+
+class MaskArgs(C.Structure):
+    _fields_ = [("x", vp), ("lens", vp), ("ld", i64), ("bs", i64)] + [(n, i32) for n in ("B", "T", "C", "dtype")]
 
 
 class VqArgs(C.Structure):
@@ -221,7 +237,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_lstm_state_reset", "stzs_predictor_prep",
            "stzs_durations", "stzs_alignment", "stzs_gather_rows", "stzs_adain_dwup", "stzs_f0n_down",
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
-           "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_code_quantize",
+           "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_mask_rows", "stzs_code_quantize",
            "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler",
            "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
@@ -278,6 +294,7 @@ def load():
         "stzs_log_mel": ([P(LogMelArgs), vp], i32),
         "stzs_stft_logmel": ([P(StftMelArgs), vp], i32),
         "stzs_pool_rows": ([P(PoolArgs), vp], i32),
+        "stzs_mask_rows": ([P(MaskArgs), vp], i32),
         "stzs_code_quantize": ([P(VqArgs), vp], i32),
         "stzs_dn_cond_steps": ([vp, vp, vp, i32, i32, i32, vp], i32),
         "stzs_dn_cond_steps_f32": ([vp, vp, vp, i32, i32, i32, vp], i32),

@@ -223,6 +223,23 @@ def check_text_lens(text_lens, B: int, T: int) -> torch.Tensor:
     return t.to(torch.int32)
 
 
+def check_ref_lens(ref_lens, B: int, N: int, n_fft: int) -> torch.Tensor:
+    """host-side check of a ragged reference batch's per-row sample counts -> int32 [B] host tensor.  ref_lens: a
+    host tensor or a sequence of B integers, each in [n_fft / 2 + 1, N] (the shortest clip the STFT's reflect padding
+    is defined on; N the padded width of ref_wav); anything else raises ValueError.  (A device tensor is never
+    checked -- that would be a sync -- the kernels clamp what they read.)"""
+    t = torch.as_tensor(ref_lens)
+    if t.device.type != "cpu":
+        raise ValueError("check_ref_lens takes host lengths")
+    if t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"ref_lens must be {B} integers (one per reference row), got {tuple(t.shape)} {t.dtype}")
+    lo = n_fft // 2 + 1
+    if B and (int(t.min()) < lo or int(t.max()) > N):
+        raise ValueError(f"ref_lens must lie in [{lo}, {N}] (reflect padding needs more than n_fft / 2 samples; "
+                         f"{N} is the padded width), got {t.tolist()}")
+    return t.to(torch.int32)
+
+
 def sigma_schedule(spec: Spec, steps: int):
     """Distilled pins 1: [smax, 0], 2: [smax, 0.5, 0]; otherwise Karras(rho) + trailing 0 (a1)."""
     if steps == 1:
@@ -938,16 +955,36 @@ class StyleTTSZS:
         h = self.act("te.h", B, T, S.d_txt, self.adt)
         return self.lstm(W.te_lstm, e, h, "te.lstm", lens=lens)
 
-    def log_mel(self, wav: torch.Tensor, dtype=None) -> Act:
+    def ref_lens(self, ref_lens, B: int, N: int):
+        """the per-row sample counts of a ragged reference batch as an int32 [B] device tensor (None stays None):
+        host lengths are range-checked (check_ref_lens) and uploaded, a device tensor is taken as it is -- no sync,
+        so a front given one stays capturable; the kernels clamp what they read into [mel_nfft / 2 + 1, N]."""
+        if ref_lens is None:
+            return None
+        if isinstance(ref_lens, torch.Tensor) and ref_lens.device.type != "cpu":
+            if ref_lens.dtype != torch.int32 or tuple(ref_lens.shape) != (B,) or not ref_lens.is_contiguous():
+                raise ValueError(f"device ref_lens must be a contiguous int32 [{B}] tensor")
+            return ref_lens
+        host = check_ref_lens(ref_lens, B, N, self.spec.mel_nfft)
+        dev = self.buf("ref_lens", (B,), torch.int32)
+        dev.copy_(host)
+        return dev
+
+    def log_mel(self, wav: torch.Tensor, dtype=None, ref_lens=None) -> Act:
         """reference wav fp32 [B, N] (device) -> log-mel [B, N/hop + 1, n_mels]:
         windowed reflect-padded frames -> bf16 DFT GEMM on MFMA (cos | -sin basis, fp32 out) -> power, sparse
         mel filterbank, log (csrc/frontend.hip); precise_frontend: one stzs_stft_logmel launch (csrc/stftmel.hip).
-        dtype of the rows: bf16 | fp32, default the front end's own (fp32 when precise_frontend)."""
+        dtype of the rows: bf16 | fp32, default the front end's own (fp32 when precise_frontend).
+        ref_lens: row b is computed as alone on wav[b, :ref_lens[b]] -- its own reflection, its own
+        F_b = ref_lens[b] // hop + 1 frames -- rows t >= F_b of the log-mel are zeros and samples past the length are
+        never read.  The STFT launch leaves the F_b in the cached int32 buffer "fe.f_lens" (no host arithmetic)."""
         S, W = self.spec, self.W
         B, N = wav.shape
         Fr = N // S.hop + 1
         if dtype is None:
             dtype = torch.float32 if self.precise_frontend else torch.bfloat16
+        lens = self.ref_lens(ref_lens, B, N)
+        flens = self.buf("fe.f_lens", (B,), torch.int32) if lens is not None else None
         if self.precise_frontend:
             # one launch, everything in fp32: the frame, an FFT in LDS, power, mel, log (csrc/stftmel.hip)
             mel = self.act("fe.mel", B, Fr, S.n_mels, dtype)
@@ -957,6 +994,8 @@ class StyleTTSZS:
             a.ldw, a.ldy, a.bsy = N, mel.ld, mel.bs
             a.B, a.N, a.F, a.n_fft, a.win, a.hop = B, N, Fr, S.mel_nfft, S.mel_win, S.hop
             a.n_mels, a.out_dtype = S.n_mels, mel.dt
+            if lens is not None:
+                a.n_lens, a.f_lens_out = lens.data_ptr(), flens.data_ptr()
             self._call(self.lib.stzs_stft_logmel, a, "stft_logmel")
             return mel
         dft = W.fe_dft
@@ -965,6 +1004,8 @@ class StyleTTSZS:
         a.wav, a.window, a.y = wav.data_ptr(), W.t(W.fe_win).data_ptr(), frames.ptr
         a.ldw, a.ldy, a.bsy = N, frames.ld, frames.bs
         a.B, a.N, a.F, a.n_fft, a.win, a.hop = B, N, Fr, S.mel_nfft, S.mel_win, S.hop
+        if lens is not None:
+            a.n_lens, a.f_lens_out = lens.data_ptr(), flens.data_ptr()
         self._call(self.lib.stzs_stft_frames, a, "stft_frames")
         nbin = S.mel_nfft // 2 + 1
         spec = self.act("fe.spec", B, Fr, 2 * nbin, torch.float32)
@@ -974,15 +1015,18 @@ class StyleTTSZS:
         a.spec, a.fb, a.ranges, a.y = spec.ptr, W.t(W.fe_fb).data_ptr(), W.t(W.fe_rng).data_ptr(), mel.ptr
         a.lds, a.bss, a.ldy, a.bsy = spec.ld, spec.bs, mel.ld, mel.bs
         a.B, a.F, a.nbin, a.n_mels, a.out_dtype = B, Fr, nbin, S.n_mels, mel.dt
+        # (the zero tail frames leave zero spec rows, whose log-mel would be log(1e-5), not the convs' zero padding)
+        a.lens = flens.data_ptr() if flens is not None else None
         self._call(self.lib.stzs_log_mel, a, "log_mel")
         return mel
 
-    def prompt_encode(self, ref_wav: torch.Tensor, prompt_idx: torch.Tensor = None) -> torch.Tensor:
+    def prompt_encode(self, ref_wav: torch.Tensor, prompt_idx: torch.Tensor = None, ref_lens=None) -> torch.Tensor:
         """reference-prompt front end on HIP: ref wav [B, N] -> DISCRETE style codes
         (README.md:5): log-mel -> 2 x (k5 conv + LeakyReLU 0.2) -> adaptive average pool to L_s rows ->
         projection -> product VQ (stzs_code_quantize).  Returns the dequantised codes fp32 [B, L_s, code];
         the indices stay in self.prompt_idx [B, L_s, G] (int32).  prompt_idx: teacher-forced indices (the
-        front end is skipped, the codebook rows are gathered)."""
+        front end is skipped, the codebook rows are gathered; ref_lens is then ignored, as ref_wav is).
+        ref_lens: per-row sample counts of a ragged reference batch (prompt_features)."""
         S, W = self.spec, self.W
         G = S.code_dim // S.vq_group
         if prompt_idx is not None:
@@ -993,7 +1037,7 @@ class StyleTTSZS:
             self.code_quantize(None, idx, out, lookup=True)
             self.prompt_idx = idx
             return out
-        z = self.prompt_features(ref_wav)
+        z = self.prompt_features(ref_wav, ref_lens)
         B = z.shape[0]
         idx = self.buf("prompt.idx", (B, S.L_s, G), torch.int32)
         out = self.buf("prompt", (B, S.L_s, S.code_dim), torch.float32)
@@ -1012,23 +1056,37 @@ class StyleTTSZS:
         a.R, a.G, a.K, a.dg, a.lookup = idx.shape[0] * idx.shape[1], G, S.vq_size, S.vq_group, int(lookup)
         self._call(self.lib.stzs_code_quantize, a, "code_quantize")
 
-    def prompt_features(self, ref_wav: torch.Tensor) -> torch.Tensor:
-        """ref wav [B, N] -> continuous prompt codes fp32 [B, L_s, code] (before the quantiser)."""
+    def prompt_features(self, ref_wav: torch.Tensor, ref_lens=None) -> torch.Tensor:
+        """ref wav [B, N] -> continuous prompt codes fp32 [B, L_s, code] (before the quantiser).
+        ref_lens: int [B] (host: range-checked; int32 device tensor: trusted, no sync), each in
+        [mel_nfft / 2 + 1, N] -- a ragged reference batch: row b is computed as alone on ref_wav[b, :ref_lens[b]]
+        (what lies past it is never read).  The log-mel carries the lengths (log_mel); the convs run over the padded
+        block and need none: zero log-mel tail rows are the zero padding pe.conv0 sees at a clip's end, one
+        stzs_mask_rows launch makes the tail rows of its output (LeakyReLU(bias)) that padding for pe.conv1, what
+        pe.conv1 leaves in its own tail rows is never read, and the pool averages each row over its own frames."""
         S, W = self.spec, self.W
         wav = ref_wav.to(self.device, torch.float32).contiguous()
         B = wav.shape[0]
-        mel = self.log_mel(wav)
+        lens = self.ref_lens(ref_lens, B, wav.shape[1])
+        mel = self.log_mel(wav, ref_lens=lens)
+        flens = self.buf("fe.f_lens", (B,), torch.int32) if lens is not None else None  # (written by the STFT launch)
         Fr = mel.T
         # (precise_frontend: fp32 rows; the convs then take the split-operand route on the weights' hi | lo streams)
         fdt = torch.float32 if self.precise_frontend else torch.bfloat16
         c0 = self.act("fe.c0", B, Fr, S.pe_ch, fdt)
         c1 = self.act("fe.c1", B, Fr, S.pe_ch, fdt)
         self.conv(W.pe_conv0, mel, c0, pad=2, epi_act=L.ACT_LEAKY, epi_slope=0.2, what="pe.conv0")
+        if flens is not None:
+            a = L.MaskArgs()
+            a.x, a.lens, a.ld, a.bs = c0.ptr, flens.data_ptr(), c0.ld, c0.bs
+            a.B, a.T, a.C, a.dtype = B, Fr, S.pe_ch, c0.dt
+            self._call(self.lib.stzs_mask_rows, a, "mask_rows")
         self.conv(W.pe_conv1, c0, c1, pad=2, epi_act=L.ACT_LEAKY, epi_slope=0.2, what="pe.conv1")
         pooled = self.act("fe.pool", B, S.L_s, S.pe_ch, fdt)
         a = L.PoolArgs()
         a.x, a.y, a.ldx, a.bsx, a.ldy, a.bsy = c1.ptr, pooled.ptr, c1.ld, c1.bs, pooled.ld, pooled.bs
         a.B, a.T, a.L, a.C, a.in_dtype, a.out_dtype = B, Fr, S.L_s, S.pe_ch, c1.dt, pooled.dt
+        a.lens = flens.data_ptr() if flens is not None else None
         self._call(self.lib.stzs_pool_rows, a, "pool_rows")
         out = self.buf("prompt.z", (B, S.L_s, S.code_dim), torch.float32)
         self.conv(W.pe_proj, pooled, Act(out), what="pe.proj")
@@ -1962,11 +2020,17 @@ class StyleTTSZS:
         t.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         return t
 
-    def encode_inputs(self, tokens, ref_wav, prompt_idx=None, text_lens=None):
-        """text encoder || prompt encoder (independent; forked when branch_streams) -> (h_txt, prompt codes)."""
+    def encode_inputs(self, tokens, ref_wav, prompt_idx=None, text_lens=None, ref_lens=None):
+        """text encoder || prompt encoder (independent; forked when branch_streams) -> (h_txt, prompt codes).
+        ref_lens: per-row sample counts of a ragged reference batch; host lengths are checked and uploaded here, on
+        the current stream, before the fork (the forked prompt branch waits on it)."""
         ref = None if ref_wav is None else ref_wav.to(self.device)
+        if prompt_idx is not None or ref is None:
+            ref_lens = None  # (teacher-forced codes: the reference and its lengths are unused)
+        else:
+            ref_lens = self.ref_lens(ref_lens, ref.shape[0], ref.shape[1])
         return self.fork("enc", lambda: self.text_encode(tokens, text_lens),
-                         lambda: self.prompt_encode(ref, prompt_idx))
+                         lambda: self.prompt_encode(ref, prompt_idx, ref_lens))
 
     def capture(self, fn):
         """Capture `fn()` into one HIP graph.  fn must be replay-safe: device-resident inputs, cached
@@ -1992,26 +2056,30 @@ class StyleTTSZS:
         return torch.cuda.is_current_stream_capturing()
 
     def synth(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None, codes=None,
-              n_frames=None, prompt_idx=None, check=True, text_lens=None):
+              n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None):
         """tokens int [B, T_txt]; ref_wav fp32 [B|1, N]; noise fp32 [B, L_s, code]; durations int [B, T_txt]
         (host tensor, or device tensor + n_frames: no device sync); seeds: per-utterance source-noise
         seeds; prompt_idx: teacher-forced discrete prompt codes [B|1, L_s, G] (ref_wav then unused).
         text_lens: int [B] (host: range-checked; int32 device tensor: trusted, no sync), each in [1, T_txt] -- a
         ragged batch: row b is computed as alone on its first text_lens[b] tokens (DESIGN.md "Ragged text
         batches").  The decoder is not ragged: the rows must still share one frame count.
+        ref_lens: int [B|1], one per row of ref_wav (host: range-checked; int32 device tensor: trusted, no sync), each
+        in [mel_nfft / 2 + 1, N] -- a ragged reference batch: row b's prompt is computed as alone on
+        ref_wav[b, :ref_lens[b]], what lies past it is never read; ignored, as ref_wav is, when
+        prompt_idx is given.
         check: raise RuntimeError if an LSTM exchange of this call timed out (its durations / prosody would be
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
         -> dict(wav=[B, 600*T40], prompt_idx=[B|1, L_s, G], status=int32 [1], ...)"""
         h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                                   n_frames, prompt_idx, text_lens)
+                                                   n_frames, prompt_idx, text_lens, ref_lens)
         wav = self.decode(pro, codes, seeds)
         if check and not self._capturing():
             self.check_status()
         return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
 
     def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx,
-               text_lens=None):
+               text_lens=None, ref_lens=None):
         """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
         encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
         -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
@@ -2020,7 +2088,7 @@ class StyleTTSZS:
         tokens = tokens.to(dev, torch.int32) if tokens.device != dev or tokens.dtype != torch.int32 else tokens
         B = tokens.shape[0]
         text_lens = self.text_lens(text_lens, B, tokens.shape[1])  # (host lengths: checked and uploaded once)
-        h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx, text_lens)
+        h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx, text_lens, ref_lens)
         if prompt.shape[0] == 1 and B > 1:
             pe = self.buf("prompt.bc", (B, S.L_s, S.code_dim), torch.float32)
             pe.copy_(prompt.expand(B, -1, -1))
@@ -2032,7 +2100,7 @@ class StyleTTSZS:
 
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
                      codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None,
-                     text_lens=None):
+                     text_lens=None, ref_lens=None):
         """configs[4] long-form synthesis with the streaming iSTFT decoder: the text,
         style, prosody and conv stack run over the whole target (AdaIN instance statistics are
         utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
@@ -2042,7 +2110,7 @@ class StyleTTSZS:
         the first chunk is ready after the front and one window's decode."""
         S = self.spec
         _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                              n_frames, prompt_idx, text_lens)
+                                              n_frames, prompt_idx, text_lens, ref_lens)
         if chunked_halo is not None:  # the chunked decoder: chunk-local statistics, first audio after one window
             yield from self.decode_chunked(pro, codes, seeds, max(1, int(round(chunk_s * S.sr / S.frame40))),
                                            int(chunked_halo))

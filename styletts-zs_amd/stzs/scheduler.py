@@ -21,6 +21,13 @@ run phase 1 as ONE batch padded to its longest text, each row with its own lengt
 computed as alone on its first text_lens[b] tokens, DESIGN.md "Ragged text batches"), and the per-utterance rows
 are cut back to their own length before phase 2.  Mixed-length traffic then takes one phase-1 pass per reference
 length instead of one per (token count, reference length).
+
+ragged_ref=True (off by default) drops the reference length from the key in the same way: the references of a chunk
+are zero-padded to its longest and each row's own sample count goes down as the engine's ref_lens (row b's prompt is
+computed as alone on its first ref_lens[b] samples, the padding is never read: DESIGN.md §2c).  With both flags on the
+key is (forced,) alone -- phase 1 is one batch per max_batch requests on any traffic; with both off the schedule is,
+call for call, the uniform one.  The padded block is as wide as the chunk's longest reference: the share of it that
+is padding is work this design accepts (requests are not sorted by reference length inside a chunk).
 """
 from __future__ import annotations
 
@@ -45,9 +52,9 @@ class Request:
 
 class BucketScheduler:
     def __init__(self, engine: StyleTTSZS, max_batch: int = 64, steps: int = 2, cfg_scale: float = 5.0,
-                 ragged_text: bool = False):
+                 ragged_text: bool = False, ragged_ref: bool = False):
         self.eng, self.max_batch, self.steps, self.cfg = engine, max_batch, steps, cfg_scale
-        self.ragged_text = ragged_text
+        self.ragged_text, self.ragged_ref = ragged_text, ragged_ref
         self.stats = {}
 
     def _chunks(self, ids):
@@ -56,11 +63,14 @@ class BucketScheduler:
 
     def phase1_groups(self, reqs: List[Request]):
         """the phase-1 batches of reqs, in launch order -> [(forced durations?, [request indices])], each of at most
-        max_batch requests that share (token count, reference length, forced) -- or, with ragged_text, only
-        (reference length, forced).  Pure host bookkeeping (reads shapes only)."""
+        max_batch requests that share (token count, reference length, forced); ragged_text takes the token count out
+        of the key, ragged_ref the reference length (both: (forced,) alone).  Pure host bookkeeping (reads shapes
+        only)."""
         g1 = OrderedDict()
         for i, r in enumerate(reqs):
-            key = (int(r.ref_wav.shape[0]), r.durations is not None)
+            key = (r.durations is not None,)
+            if not self.ragged_ref:
+                key = (int(r.ref_wav.shape[0]),) + key
             if not self.ragged_text:
                 key = (int(r.tokens.shape[0]),) + key
             g1.setdefault(key, []).append(i)
@@ -69,9 +79,11 @@ class BucketScheduler:
     def synth(self, reqs: List[Request]) -> List[torch.Tensor]:
         """-> one fp32 waveform [600 * T40_i] per request, in request order (device tensors)."""
         eng, S, dev = self.eng, self.eng.spec, self.eng.device
-        # ---- phase 1: text / prompt / style / durations, grouped by (T_txt, N_ref) -- ragged_text: by N_ref ----
+        # ---- phase 1: text / prompt / style / durations, grouped by (T_txt, N_ref) -- ragged_text: without T_txt,
+        # ragged_ref: without N_ref ----
         per = [None] * len(reqs)
         n1 = 0
+        ref_n = pad_n = 0  # reference samples of the phase-1 blocks, and how many of them are padding
         t1 = time.perf_counter()  # (every phase-1 batch ends in a host sync: the wall time is the phase's)
         for forced, ch in self.phase1_groups(reqs):
             n1 += 1
@@ -88,16 +100,27 @@ class BucketScheduler:
             else:
                 tok = torch.stack([reqs[i].tokens for i in ch]).to(dev, torch.int32)
                 dur_ov = torch.stack([reqs[i].durations for i in ch]) if forced else None
-            ref = torch.stack([reqs[i].ref_wav for i in ch]).to(dev, torch.float32)
+            nl = [int(reqs[i].ref_wav.shape[0]) for i in ch]
+            Nm = max(nl)
+            rlens = None
+            if self.ragged_ref and min(nl) < Nm:
+                # pad to the chunk's longest reference (zeros: never read) and hand the rows' own sample counts down
+                ref = torch.stack([torch.nn.functional.pad(reqs[i].ref_wav, (0, Nm - reqs[i].ref_wav.shape[0]))
+                                   for i in ch]).to(dev, torch.float32)
+                rlens = eng.ref_lens(nl, len(ch), Nm)
+                pad_n += Nm * len(ch) - sum(nl)
+            else:
+                ref = torch.stack([reqs[i].ref_wav for i in ch]).to(dev, torch.float32)
+            ref_n += Nm * len(ch)
             eps = torch.stack([reqs[i].noise for i in ch]).to(dev, torch.float32)
-            if lens is None:  # (the uniform path, call for call as before)
+            if lens is None and rlens is None:  # (the uniform path, call for call as before)
                 h = eng.text_encode(tok)
                 prompt = eng.prompt_encode(ref)
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg)
                 du = eng.predict_durations(h, codes, dur_ov)
             else:
                 h = eng.text_encode(tok, lens)
-                prompt = eng.prompt_encode(ref)
+                prompt = eng.prompt_encode(ref, ref_lens=rlens)
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg, lens)
                 du = eng.predict_durations(h, codes, dur_ov, lens)
             tot = du["dur"].to(torch.int64).sum(1).cpu()  # host sync: frame counts decide phase 2
@@ -131,5 +154,6 @@ class BucketScheduler:
                     out[i] = wav[j].clone()
         eng.check_status()  # the phase-2 prosody LSTMs
         self.stats = dict(requests=len(reqs), phase1_batches=n1, phase2_batches=n2,
-                          frame_buckets=sorted(g2.keys()), phase1_ms=1e3 * t1)
+                          frame_buckets=sorted(g2.keys()), phase1_ms=1e3 * t1,
+                          ref_pad_share=pad_n / max(ref_n, 1))
         return out

@@ -5,7 +5,8 @@ whose dumps are equal enqueue the same launches with the same argument structs: 
 
     python tools/launch_trace.py --spec v0 --dump a.jsonl      # one line per case: name, calls, launches, sha256
 
-Recorded per call: the function name and per argument the struct's fields (pointer fields as null / ptr), the elements
+Recorded per call: the function name and per argument the struct's fields (pointer fields as null / ptr; an optional
+pointer of type stzs._lib.opt_vp only when it is set, so a new optional field leaves the digests alone), the elements
 of a struct array, or the scalar (integers >= 2^24 are addresses: "ptr"); each case ends with one "buffers" record,
 the engine's buffer and scratch keys in the order they were first requested.  Stub results: *_workspace queries a fixed
 size, stzs_conv1d_group its count, stzs_istft_stream_span a fixed arithmetic span, everything else 0.
@@ -47,6 +48,10 @@ def _struct(s):
     out = {}
     for name, typ in s._fields_:
         v = getattr(s, name)
+        if typ is getattr(_lib, "opt_vp", None):  # an optional pointer: recorded when set (NULL: the call without it)
+            if v.value:
+                out[name] = "ptr"
+            continue
         out[name] = ("ptr" if v else "null") if typ is C.c_void_p else _scalar(v)
     return out
 
