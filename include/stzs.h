@@ -126,6 +126,22 @@ typedef struct stzs_conv_args {
     int64_t pro_ld;
     int32_t pro_nch, pro_T;
     float pro_eps, pad_pp;
+    /* optional ragged frame batch (NULL = the launch as before, every bit): t_lens int32 [B] on the device, utterance
+     * b holds T_b = clamp(t_lens[b] * mul, 1, T_in) rows, mul = 2 when t_lens_mul == 2 (the 80-fps rows behind the
+     * x2 upsampling block, lengths still counted in 40-fps frames) and 1 when it is 0 or 1.  T_b replaces T_in for
+     * utterance b: staged rows tin >= T_b are zeros after the prologue (the zero padding a conv sees at the end of a
+     * sequence of T_b rows), no load address leaves [0, T_b) -- x, res (at t / res_tdiv) and acc_in rows at or past
+     * T_b are never read -- and with stat_part only stored rows t < T_b enter the partials (a 64-row chunk wholly
+     * past T_b holds exact zeros, so stzs_chan_stats_final with the same lengths adds zeros to the sums of the
+     * utterance alone).  y[b, t < T_b] and the partial chunks below ceil(T_b / 64) are the bits of utterance b
+     * launched alone with T_in = T_out = T_b; y[b, t >= T_b] is finite and unspecified.
+     * Requires stride 1, T_out == T_in, ups 0, per-utterance tiles (not a plain linear), no split-K, no pro_part, the
+     * vector epilogue (Co, ldy, bsy, ldr, bsr, lda, bsa multiples of 8).  Honoured by the generic conv (flags 0 but
+     * STZS_CONV_LINEAR_IDS; x and y both bf16 or both fp32; prologue activation NONE or LEAKY) and by the
+     * register-direct k3 LeakyReLU / identity form (STZS_CONV_W_FRAG32, ks 3, no acc_in: narrow at 128- and 64-row
+     * tiles, and wide); every other form returns STZS_EINVAL before any HIP call, stzs_conv1d_group likewise. */
+    const int32_t* t_lens;
+    int32_t t_lens_mul, pad_tl;
 } stzs_conv_args;
 /* split-K workspace of a linear over `rows` flat rows: fp32 slab bytes; the tile (= counter) count is
  * bytes / (splitk * 32768).  0 for a bad argument. */
@@ -233,6 +249,13 @@ typedef struct stzs_stats_args {
     int64_t ld, bs, stat_bs;
     int32_t B, T, C, dtype;
     float eps, pad_f;
+    /* optional ragged frame batch (NULL = the launch as before): lens int32 [B] on the device, utterance b holds
+     * T_b = clamp(lens[b] * mul, 1, T) rows (mul = 2 when lens_mul == 2, else 1).  The partial pass reads rows < T_b
+     * only (a 256-row chunk wholly past T_b gets zero partials), the finaliser divides by T_b: mean and rstd of
+     * utterance b are the bits of a launch on it alone with T = T_b (the fp64 group sums only add exact zeros for the
+     * chunks past T_b).  Honoured by stzs_chan_stats, _partial, _final and _final_group. */
+    const int32_t* lens;
+    int32_t lens_mul, pad_l;
 } stzs_stats_args;
 size_t stzs_chan_stats_workspace(int B, int T, int C);
 int stzs_chan_stats(const stzs_stats_args* a, void* stream);
@@ -429,6 +452,11 @@ typedef struct stzs_dwup_args {
     int64_t ldx, bsx, ldy, bsy, stat_bs, gb_bs, gb_beta_off;
     int32_t B, T, C, dtype; /* dtype of x and y: STZS_BF16 | STZS_F32 */
     float slope, pad_f;
+    /* optional ragged frame batch (NULL = the launch as before): lens int32 [B] on the device in INPUT rows,
+     * T_b = clamp(lens[b], 1, T).  Output rows < 2 T_b are the bits of utterance b alone at T = T_b (the odd row
+     * 2 T_b - 1 has no right neighbour), output rows >= 2 T_b are stored as exact zeros, input rows >= T_b are not
+     * read. */
+    const int32_t* lens;
 } stzs_dwup_args;
 int stzs_adain_dwup(const stzs_dwup_args* a, void* stream);
 

@@ -40,6 +40,14 @@ STZS_DEV void stat_finish(double s, double q, int T, float eps, float& mu, float
     rs = (float)(1.0 / __dsqrt_rn(var + (double)eps));
 }
 
+// ragged frame batch: utterance b's own row count from a device length (times 2 when mul == 2: the 80-fps rows behind
+// the x2 upsampling block), clamped into [1, T] BEFORE it bounds anything -- a bad value never becomes an address.
+// (the multiply in 64 bits: a garbage length cannot wrap into range)
+STZS_DEV int rag_rows(const int32_t* lens, int b, int mul, int T) {
+    const long v = (long)lens[b] * (mul == 2 ? 2 : 1);
+    return v < 1 ? 1 : (v > T ? T : (int)v);
+}
+
 STZS_DEV int xcd_remap(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);

@@ -22,6 +22,8 @@
 //    ReflectionPad(1,0) when ups > 0.
 #include "conv_common.hpp"
 
+#include <type_traits>
+
 int stzs_gemm_glds_launch(const stzs_conv_args& a, hipStream_t s);   // csrc/gemm.hip
 int stzs_conv_x3_launch(const stzs_conv_args* a, hipStream_t s);     // csrc/convx.hip
 int stzs_conv_f32_launch(const stzs_conv_args* a, hipStream_t s);    // csrc/convx.hip
@@ -37,8 +39,12 @@ namespace {
 // other slice's 64-KB slab through ONE workgroup: 7.5 us of a 24-us batch-1 decoder conv, tools/conv_phase.py).
 // (r06) the body as an always-inlined device function of (arguments by value, split-K slice zs): conv_mfma is this
 // body with zs = grid z, conv_mfma_pair two problems' bodies in one launch.
-template <typename TIn, typename TOut, bool FLAT, int PACT, bool DEEP = false, bool SKE = false>
+// RAG (stzs_conv_args.t_lens, a ragged frame batch; its own instantiations, so the length costs the kernels above
+// nothing): utterance bq's own row count Tin (clamped into [1, T_in]) stands in for T_in where the rows are staged --
+// rows at or past it are staged as zeros and never loaded -- and in the epilogue's residual clamp and statistics mask.
+template <typename TIn, typename TOut, bool FLAT, int PACT, bool DEEP = false, bool SKE = false, bool RAG = false>
 STZS_DEV void conv_body(const stzs_conv_args a, const int zs) {
+    static_assert(!RAG || (!FLAT && !DEEP && !SKE), "ragged rows: per-utterance tiles, no split-K");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int cic = a.cic;
     const int pitch = cic * 2 + 16;
@@ -71,6 +77,7 @@ STZS_DEV void conv_body(const stzs_conv_args a, const int zs) {
         bq = bx / tpb;
         t0 = (bx - bq * tpb) * BT;
     }
+    const int Tin = RAG ? rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_in) : a.T_in;  // (uniform per workgroup)
     const int nchunk = a.ci_pad / cic;
     const int kpc = cic >> 5;
     const int NK = nchunk * ks * kpc;
@@ -156,8 +163,8 @@ STZS_DEV void conv_body(const stzs_conv_args a, const int zs) {
                     off = bb * a.bsx + (R - bb * a.T_in) * a.ldx + cic0;
                 } else {
                     int tin = t0 * a.stride - a.pad + r;
-                    ok = ok && tin >= 0 && tin < a.T_in;
-                    tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+                    ok = ok && tin >= 0 && tin < Tin;
+                    tin = tin < 0 ? 0 : (tin >= Tin ? Tin - 1 : tin);
                     off = (long)bq * a.bsx + (long)tin * a.ldx + cic0;
                 }
                 okv[i] = ok;
@@ -290,7 +297,7 @@ STZS_DEV void conv_body(const stzs_conv_args a, const int zs) {
         return;
     }
     CPROF(5)
-    finish<TOut, FLAT>(a, acc, smem, bq, t0, row0, by);
+    finish<TOut, FLAT, BT, -1, RAG>(a, acc, smem, bq, t0, row0, by);
     CPROF(6)
     CPROF_RT(14)
 #ifdef STZS_CONV_PROF
@@ -301,9 +308,9 @@ STZS_DEV void conv_body(const stzs_conv_args a, const int zs) {
 #endif
 }
 
-template <typename TIn, typename TOut, bool FLAT, int PACT, bool DEEP = false, bool SKE = false>
+template <typename TIn, typename TOut, bool FLAT, int PACT, bool DEEP = false, bool SKE = false, bool RAG = false>
 __global__ __launch_bounds__(NTHR, DEEP ? 1 : 2) void conv_mfma(const stzs_conv_args a) {
-    conv_body<TIn, TOut, FLAT, PACT, DEEP, SKE>(a, blockIdx.z);
+    conv_body<TIn, TOut, FLAT, PACT, DEEP, SKE, RAG>(a, blockIdx.z);
 }
 
 // (r06) two independent DEEP split-K convs of one shape (the prosody predictor's F0 and N branches at batch 1) in one
@@ -543,6 +550,18 @@ int launch_dt(const stzs_conv_args& a, hipStream_t s) {
     dim3 grid(gx, a.co_pad / BCO);
     if (flat && a.stat_part) return STZS_EINVAL;  // fused statistics: per-utterance tiles only
     void (*k)(stzs_conv_args);
+    if (a.t_lens) {
+        // ragged frame batch (stzs_conv_check has refused a plain linear, split-K, pro_part, strides, ConvTranspose and
+        // every flag that leaves this path): x and y of one dtype, NONE / LEAKY prologue, the vector epilogue
+        if constexpr (!F8 && std::is_same<TIn, TOut>::value) {
+            if (flat || a.splitk > 1 || a.pro_act == STZS_ACT_SNAKE || !epi_vec(a)) return STZS_EINVAL;
+            k = a.pro_act == STZS_ACT_LEAKY ? conv_mfma<TIn, TOut, false, STZS_ACT_LEAKY, false, false, true>
+                                            : conv_mfma<TIn, TOut, false, STZS_ACT_NONE, false, false, true>;
+            return stzs_launch(k, grid, dim3(NTHR), lds, s, a);
+        } else {
+            return STZS_EINVAL;
+        }
+    }
     if (F8 || (flat && sizeof(TIn) == 2 && (a.flags & STZS_CONV_A_DMA) && a.pro_cscale == 1.f))
         return stzs_gemm_glds_launch(a, s);  // (csrc/gemm.hip)
     if (a.splitk > 1) {  // conv_mfma: split over input-channel chunks (2..16 slices, at least one chunk each)

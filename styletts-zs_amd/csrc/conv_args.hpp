@@ -13,23 +13,26 @@ static inline bool stzs_plain_linear(const stzs_conv_args& a) {
 
 // The weight forms, in routing order: the first row whose bit is set in a.flags names the launcher (the last row, bit
 // 0, is the generic conv_mfma / gemm_glds path).  `excludes`: flag bits that are an error (STZS_EINVAL) beside it;
-// `splitk`: whether the form has a split-K variant; `taps`: whether it reads ks / dil / stride (a ROWS linear does not).
+// `splitk`: whether the form has a split-K variant; `taps`: whether it reads ks / dil / stride (a ROWS linear does not);
+// `t_lens`: whether the form has kernels that honour the ragged frame lengths (stzs_conv_args.t_lens: the generic
+// conv_mfma path without STZS_CONV_A_DMA, and the register-direct form's k3 LeakyReLU / identity block convs --
+// stzs_conv_check holds the rule common to both, each launcher what is particular to its kernels).
 // Only the generic path takes prologue statistics from partials (pro_part), and not with STZS_CONV_A_DMA.
 struct stzs_conv_form {
     int bit, excludes;
-    bool splitk, taps;
+    bool splitk, taps, t_lens;
 };
 constexpr int STZS_CONV_OLD_FORMS = STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32;
 constexpr stzs_conv_form STZS_CONV_FORMS[] = {
     {STZS_CONV_W_FRAG32X3, STZS_CONV_OLD_FORMS | STZS_CONV_W_X3 | STZS_CONV_A_DMA | STZS_CONV_W_FRAG32 | STZS_CONV_ROWS |
-                               STZS_CONV_UPS_NOISE, false, true},                      // csrc/mrfx.hip
-    {STZS_CONV_W_FRAG32, STZS_CONV_OLD_FORMS | STZS_CONV_A_DMA, false, true},         // csrc/mrfv.hip, csrc/ups.hip
-    {STZS_CONV_ROWS, STZS_CONV_OLD_FORMS | STZS_CONV_W_X3, true, false},              // csrc/rows.hip
-    {STZS_CONV_W_X3, STZS_CONV_OLD_FORMS, false, true},                               // csrc/convx.hip conv_x3
-    {STZS_CONV_W_F32, STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32, false, true},        // csrc/convx.hip conv_f32
-    {STZS_CONV_W_LANE16, 0, false, true},                                             // csrc/mrf.hip mrf_conv
-    {STZS_CONV_W_NARROW32, 0, false, true},                                           // csrc/mrf.hip narrow_conv
-    {0, 0, true, true},                                                               // csrc/conv.hip, csrc/gemm.hip
+                               STZS_CONV_UPS_NOISE, false, true, false},                    // csrc/mrfx.hip
+    {STZS_CONV_W_FRAG32, STZS_CONV_OLD_FORMS | STZS_CONV_A_DMA, false, true, true},   // csrc/mrfv.hip, csrc/ups.hip
+    {STZS_CONV_ROWS, STZS_CONV_OLD_FORMS | STZS_CONV_W_X3, true, false, false},       // csrc/rows.hip
+    {STZS_CONV_W_X3, STZS_CONV_OLD_FORMS, false, true, false},                        // csrc/convx.hip conv_x3
+    {STZS_CONV_W_F32, STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32, false, true, false},       // csrc/convx.hip conv_f32
+    {STZS_CONV_W_LANE16, 0, false, true, false},                                      // csrc/mrf.hip mrf_conv
+    {STZS_CONV_W_NARROW32, 0, false, true, false},                                    // csrc/mrf.hip narrow_conv
+    {0, 0, true, true, true},                                                         // csrc/conv.hip, csrc/gemm.hip
 };
 // every bit that takes a call off the generic path's conv_mfma kernels (the pair launch and pro_part refuse them)
 constexpr int STZS_CONV_NOT_GENERIC = STZS_CONV_OLD_FORMS | STZS_CONV_W_X3 | STZS_CONV_W_FRAG32 | STZS_CONV_W_FRAG32X3 |

@@ -118,7 +118,9 @@ STZS_DEV float epi_act(float x, float slope) {
     else return x;
 }
 
-template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int EACT, int BTM>
+// RAG (a ragged frame batch, stzs_conv_args.t_lens; conv_mfma's own instantiations): the residual / accumulate rows
+// clamp into utterance bq's own rows and only stored rows below its count enter the statistics.
+template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int EACT, int BTM, bool RAG = false>
 STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_bias, const float* c_gate, int bq,
                        int t0, long row0, int tid, int by) {
     const TOut* Rp = reinterpret_cast<const TOut*>(a.res);
@@ -131,7 +133,8 @@ STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_
     const long nrows_flat = (long)a.B * a.T_out;
     const bool small_rows = nrows_flat + BTM < (1L << 22);
     const float invTo = 1.f / (float)a.T_out;
-    const long t_hi = ups ? (long)a.T_final + a.refl - 1 : (long)a.T_out - 1;
+    const int Tb = RAG ? rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_out) : a.T_out;
+    const long t_hi = ups ? (long)a.T_final + a.refl - 1 : (long)(RAG ? Tb : a.T_out) - 1;
     const int cv = tid & 15;
     const int n = by * BCO + cv * 8;
     const bool col_ok = n < ncol;
@@ -255,7 +258,7 @@ STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_
                 if constexpr (sizeof(TOut) == 2) {
                     const uint4 pk = pack8(o);
                     pkv[i] = pk;
-                    if (stat) {  // statistics of the value as stored (bf16-rounded)
+                    if (stat && (!RAG || t < Tb)) {  // statistics of the value as stored (bf16-rounded)
                         const uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -269,7 +272,7 @@ STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_
                 } else {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) ofv[i][j] = o[j];
-                    if (stat) {
+                    if (stat && (!RAG || t < Tb)) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
                             st_s[j] += o[j];
@@ -329,14 +332,14 @@ STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_
     }
 }
 
-template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int BTM>
+template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int BTM, bool RAG = false>
 STZS_DEV void epilogue_act(const stzs_conv_args& a, const float* ep, const float* c_bias, const float* c_gate, int bq,
                            int t0, long row0, int tid, int by) {
     switch (a.epi_act) {
-        case STZS_ACT_GELU: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_GELU, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
-        case STZS_ACT_SILU: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_SILU, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
-        case STZS_ACT_LEAKY: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_LEAKY, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
-        default: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_NONE, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
+        case STZS_ACT_GELU: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_GELU, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
+        case STZS_ACT_SILU: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_SILU, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
+        case STZS_ACT_LEAKY: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_LEAKY, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
+        default: epilogue<TOut, FLAT, VEC, HR, HA, STZS_ACT_NONE, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by); break;
     }
 }
 
@@ -346,7 +349,7 @@ STZS_DEV bool splitk_combine_rt(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][
 // 0..15: ONE vectorised variant, HR = bit 0, HA = bit 1, activation index (ep_act) = bits 2-3 (the GEMM kernels:
 // with all twenty variants inlined a gemm_glds instance was ~73 k instructions and its epilogue ran from a cold
 // instruction cache)
-template <typename TOut, bool FLAT, int BTM = BT, int EP = -1>
+template <typename TOut, bool FLAT, int BTM = BT, int EP = -1, bool RAG = false>
 STZS_DEV void finish(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][4], unsigned char* smem, int bq, int t0, long row0,
                      int by);
 constexpr int ep_act(int i) { return i == 0 ? STZS_ACT_NONE : (i == 1 ? STZS_ACT_GELU : (i == 2 ? STZS_ACT_SILU : STZS_ACT_LEAKY)); }
@@ -375,7 +378,7 @@ __host__ __device__ inline bool epi_vec(const stzs_conv_args& a) {
 #else
 #define GPROF_E(i)
 #endif
-template <typename TOut, bool FLAT, int BTM, int EP>
+template <typename TOut, bool FLAT, int BTM, int EP, bool RAG>
 STZS_DEV void finish(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][4], unsigned char* smem, int bq, int t0, long row0,
                      int by) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -404,14 +407,14 @@ STZS_DEV void finish(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][4], unsigne
     GPROF_E(6)
     CPROF(8)
     if constexpr (EP >= 0) {
-        epilogue<TOut, FLAT, true, (EP & 1) != 0, (EP & 2) != 0, ep_act(EP >> 2), BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
+        epilogue<TOut, FLAT, true, (EP & 1) != 0, (EP & 2) != 0, ep_act(EP >> 2), BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
     } else if (epi_vec(a)) {
-        if (a.res && a.acc_in) epilogue_act<TOut, FLAT, true, true, true, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
-        else if (a.res) epilogue_act<TOut, FLAT, true, true, false, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
-        else if (a.acc_in) epilogue_act<TOut, FLAT, true, false, true, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
-        else epilogue_act<TOut, FLAT, true, false, false, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
+        if (a.res && a.acc_in) epilogue_act<TOut, FLAT, true, true, true, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
+        else if (a.res) epilogue_act<TOut, FLAT, true, true, false, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
+        else if (a.acc_in) epilogue_act<TOut, FLAT, true, false, true, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
+        else epilogue_act<TOut, FLAT, true, false, false, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
     } else {
-        epilogue_act<TOut, FLAT, false, true, true, BTM>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
+        epilogue_act<TOut, FLAT, false, true, true, BTM, RAG>(a, ep, c_bias, c_gate, bq, t0, row0, tid, by);
     }
 }
 

@@ -28,20 +28,30 @@ __attribute__((visibility("hidden"))) int stzs_conv_check(const stzs_conv_args* 
     if (a->pro_act == STZS_ACT_SNAKE && !a->pro_alpha) return STZS_EINVAL;
     if (a->stat_part && !stzs_aligned(a->stat_part, 8)) return STZS_EINVAL;
     if (a->splitk > 1 && !f.splitk) return STZS_EINVAL;
+    if (a->t_lens) {
+        // ragged frame batch: a form with length-aware kernels (the generic one: not its LDS-DMA GEMM), row for row
+        // (stride 1, T_out == T_in, no ConvTranspose), per-utterance tiles (not a plain linear), no split-K, the
+        // prologue statistics finalised (no pro_part)
+        if (!f.t_lens || (a->flags & STZS_CONV_A_DMA) || a->stride != 1 || a->T_out != a->T_in || a->ups != 0 ||
+            a->splitk > 1 || a->pro_part || stzs_plain_linear(*a) || a->in_dtype == STZS_F8 || a->t_lens_mul < 0 ||
+            a->t_lens_mul > 2 || !stzs_aligned(a->t_lens, 4))
+            return STZS_EINVAL;
+    }
     return STZS_OK;
 }
 
 extern "C" int stzs_conv1d_group(const stzs_conv_args* a, int n, void* stream) {
     if (!a || n < 1 || n > 3) return STZS_EINVAL;
     const auto trio_member = [](const stzs_conv_args& p) {  // a valid FRAG32 conv (not the ConvTranspose form)
-        return stzs_conv_form_of(p.flags).bit == STZS_CONV_W_FRAG32 && p.ups <= 0 && stzs_conv_check(&p) == STZS_OK;
+        return stzs_conv_form_of(p.flags).bit == STZS_CONV_W_FRAG32 && p.ups <= 0 && !p.t_lens &&
+               stzs_conv_check(&p) == STZS_OK;  // (with t_lens: one stzs_conv1d each, refused or honoured there)
     };
     if (n == 3 && trio_member(a[0]) && trio_member(a[1]) && trio_member(a[2])) {
         const int rc = stzs_mrfv_trio_launch(a, reinterpret_cast<hipStream_t>(stream));
         if (rc == STZS_OK) return 1;
         if (rc != STZS_ESHAPE) return rc;
     }
-    if (n == 2 && !a[0].pro_part == !a[1].pro_part) {  // (pro_part: both or neither, as the body reads it uniformly)
+    if (n == 2 && !a[0].pro_part == !a[1].pro_part && !a[0].t_lens && !a[1].t_lens) {  // (pro_part: both or neither, as the body reads it uniformly)
         const int rc = stzs_conv_pair_launch(a, reinterpret_cast<hipStream_t>(stream));
         if (rc == STZS_OK) return 1;
         if (rc != STZS_ESHAPE) return rc;

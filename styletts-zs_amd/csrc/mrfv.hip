@@ -34,6 +34,9 @@ int mrfv_shape(const stzs_conv_args& a) {
         (a.acc_in && (a.lda % 8 || a.bsa % 8)) || (a.stat_part && a.stat_ld < a.Co))
         return STZS_ESHAPE;
     if (a.pro_act == STZS_ACT_SNAKE && a.res && a.res_tdiv != 1) return STZS_ESHAPE;  // (TD1 in the kernel)
+    // ragged frame batch (t_lens): the k3 LeakyReLU / identity block convs only (stzs_conv_check: the rest of the rule)
+    if (a.t_lens && (a.ks != 3 || a.acc_in || (a.pro_act != STZS_ACT_LEAKY && a.pro_act != STZS_ACT_NONE)))
+        return STZS_EINVAL;
     return STZS_OK;
 }
 
@@ -80,7 +83,7 @@ __attribute__((visibility("hidden"))) int stzs_mrfv_trio_launch(const stzs_conv_
         const stzs_conv_args& b = a[i];
         bool wide, t64;
         mrfv_tiles(b, wide, t64);
-        if (mrfv_shape(b) != STZS_OK || b.ks != KS[i] || b.pro_act != STZS_ACT_SNAKE || b.acc_in || b.alpha != 1.f || !t64 ||
+        if (mrfv_shape(b) != STZS_OK || b.t_lens || b.ks != KS[i] || b.pro_act != STZS_ACT_SNAKE || b.acc_in || b.alpha != 1.f || !t64 ||
             b.B != a[0].B || b.T_out != a[0].T_out || b.Ci != a[0].Ci || b.Co != a[0].Co || b.ci_pad != a[0].ci_pad ||
             b.co_pad != a[0].co_pad || (b.res != nullptr) != (a[0].res != nullptr))
             return STZS_ESHAPE;
@@ -115,6 +118,15 @@ __attribute__((visibility("hidden"))) int stzs_mrfv_conv_launch(const stzs_conv_
         k = wide ? (R ? mrfv_conv<STZS_ACT_NONE, true, false, 1, 0, true, 2> : mrfv_conv<STZS_ACT_NONE, false, false, 1, 0, true, 2>)
           : t64 ? (R ? mrfv_conv<STZS_ACT_NONE, true, false, 1, 0, true, 1, 64> : mrfv_conv<STZS_ACT_NONE, false, false, 1, 0, true, 1, 64>)
                  : (R ? mrfv_conv<STZS_ACT_NONE, true, false, 1, 0, true> : mrfv_conv<STZS_ACT_NONE, false, false, 1, 0, true>);
+    } else if (a.t_lens) {  // (mrfv_shape: k3, LeakyReLU / identity, no accumulate input) the lengths' own instances
+        if (a.pro_act == STZS_ACT_LEAKY)
+            k = wide ? (R ? mrfv_conv<STZS_ACT_LEAKY, true, false, 3, 0, true, 2, 128, true> : mrfv_conv<STZS_ACT_LEAKY, false, false, 3, 0, true, 2, 128, true>)
+              : t64 ? (R ? mrfv_conv<STZS_ACT_LEAKY, true, false, 3, 0, true, 1, 64, true> : mrfv_conv<STZS_ACT_LEAKY, false, false, 3, 0, true, 1, 64, true>)
+                     : (R ? mrfv_conv<STZS_ACT_LEAKY, true, false, 3, 0, true, 1, 128, true> : mrfv_conv<STZS_ACT_LEAKY, false, false, 3, 0, true, 1, 128, true>);
+        else
+            k = wide ? (R ? mrfv_conv<STZS_ACT_NONE, true, false, 3, 0, true, 2, 128, true> : mrfv_conv<STZS_ACT_NONE, false, false, 3, 0, true, 2, 128, true>)
+              : t64 ? (R ? mrfv_conv<STZS_ACT_NONE, true, false, 3, 0, true, 1, 64, true> : mrfv_conv<STZS_ACT_NONE, false, false, 3, 0, true, 1, 64, true>)
+                     : (R ? mrfv_conv<STZS_ACT_NONE, true, false, 3, 0, true, 1, 128, true> : mrfv_conv<STZS_ACT_NONE, false, false, 3, 0, true, 1, 128, true>);
     } else if (!A && a.ks == 3) {  // the AdaIN residual blocks of the decoder / prosody predictor
         if (a.pro_act == STZS_ACT_LEAKY)
             k = wide ? (R ? mrfv_conv<STZS_ACT_LEAKY, true, false, 3, 0, true, 2> : mrfv_conv<STZS_ACT_LEAKY, false, false, 3, 0, true, 2>)

@@ -113,8 +113,13 @@ __device__ unsigned long long g_mprof[8 * 16384];
 // staged operands, the K order of every output element and the 64-row statistics chunks are the same: bit-identical.
 // (r06) the body as an always-inlined device function: the kernel mrfv_conv below is this body alone (same code
 // object), mrfv_trio runs three of them in one launch.
-template <int PACT, bool HR, bool HA, int KS, int NCH, bool AL, int WPW = 1, int BT = 128>
+// RAG (stzs_conv_args.t_lens, a ragged frame batch; the k3 LeakyReLU / identity block forms only, as instantiations of
+// their own -- the Snake forms and every kernel without the lengths are unchanged): utterance bq's own row count Tin
+// (clamped into [1, T_in]) stands in for T_in in the staging clamps, the zero-padding mask and the interior test, and
+// in the epilogue's residual clamp and statistics mask.
+template <int PACT, bool HR, bool HA, int KS, int NCH, bool AL, int WPW = 1, int BT = 128, bool RAG = false>
 STZS_DEV void mrfv_body(const stzs_conv_args a) {
+    static_assert(!RAG || (PACT != STZS_ACT_SNAKE && !HA && KS == 3 && NCH == 0), "ragged rows: the k3 block convs");
     static_assert(WPW == 1 || (WPW == 2 && NCH != 1), "the wide form is for multi-chunk inputs");
     static_assert(BT == 128 || (BT == 64 && WPW == 1), "64-row tiles: narrow form");
     MPROF(5, __builtin_amdgcn_s_memrealtime())
@@ -136,6 +141,10 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
     const int by = lin / nx, bx = lin - by * nx;  // (co tile, utterance x time tile)
     const int bq = bx / tpb;
     const int t0 = (bx - bq * tpb) * BT;
+    // (every use sits behind `if constexpr (RAG)` beside the unchanged expression, so the other instantiations compile
+    // from the text they had)
+    [[maybe_unused]] int Tin = 0;
+    if constexpr (RAG) Tin = rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_in);  // (uniform per workgroup)
     const int nchunk = NCH ? NCH : a.ci_pad >> 7;
     constexpr int SB = BT == 128 ? sb_rows(KS) : sb_rows64(KS);
     // weights: [co tile][chunk][tap][kq][wave][nt][lane][8] bf16 -> 512 bf16x8 per K-step.  Wide form: wave w takes
@@ -175,7 +184,8 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
 #pragma unroll
         for (int i = 0; i < SB; ++i) {
             int tin = t0 - a.pad + rsub + 16 * i;
-            tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+            if constexpr (RAG) tin = tin < 0 ? 0 : (tin >= Tin ? Tin - 1 : tin);
+            else tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
             rawn[i] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(X) + (unsigned)(tin * (int)a.ldx + cl) * 2u);
         }
         if (tid < 128 && a.pro_mode == STZS_PRO_ADAIN) {
@@ -268,7 +278,8 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
                         raw[i] = rawe[i];  // (loaded ahead of the constants)
                     } else {
                         int tin = t0 - a.pad + rsub + 16 * i;
-                        if constexpr (!FULL) tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+                        if constexpr (!FULL && RAG) tin = tin < 0 ? 0 : (tin >= Tin ? Tin - 1 : tin);
+                        else if constexpr (!FULL) tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
                         const unsigned off = (unsigned)(tin * (int)a.ldx + cl) * 2u;
                         raw[i] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(X) + off);
                     }
@@ -307,7 +318,9 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
                             rw[4 * i + p] = pack2bf(y.x, y.y);
                         } else {
                             const int tin = t0 - a.pad + rsub + 16 * i;  // zero padding / channels past Ci
-                            const bool ok = c_ok && tin >= 0 && tin < a.T_in;
+                            bool ok;
+                            if constexpr (RAG) ok = c_ok && tin >= 0 && tin < Tin;
+                            else ok = c_ok && tin >= 0 && tin < a.T_in;
                             rw[4 * i + p] = ok ? pack2bf(y.x, y.y) : 0u;
                         }
                     }
@@ -318,7 +331,9 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
                     if (r < rows_in) *reinterpret_cast<uint4*>(smem + r * P + cv * 16) = raw[i];
                 }
             };
-            const bool interior = t0 - a.pad >= 0 && t0 - a.pad + 16 * SB <= a.T_in && cc * 128 + 128 <= a.Ci;
+            bool interior;
+            if constexpr (RAG) interior = t0 - a.pad >= 0 && t0 - a.pad + 16 * SB <= Tin && cc * 128 + 128 <= a.Ci;
+            else interior = t0 - a.pad >= 0 && t0 - a.pad + 16 * SB <= a.T_in && cc * 128 + 128 <= a.Ci;
             if (interior)
                 stage(std::integral_constant<bool, true>{});
             else
@@ -399,7 +414,9 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int t = t0 + mt * 16 + n;
-        const int tc = t < a.T_out ? t : a.T_out - 1;
+        int tc;
+        if constexpr (RAG) tc = t < Tin ? t : Tin - 1;  // (T_out == T_in: no residual row at or past Tin is read)
+        else tc = t < a.T_out ? t : a.T_out - 1;
         if constexpr (HR) {
             const int tr = TD1 ? tc : tc / a.res_tdiv;
             rr[mt] = *reinterpret_cast<const uint4*>(Rq + (unsigned)(tr * (int)a.ldr + coc) * 2u);
@@ -439,7 +456,10 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
             }
             const uint4 o = pack8(v);
             if (ok) *reinterpret_cast<uint4*>(Y + (long)bq * a.bsy + (long)t * a.ldy + coc) = o;
-            if (stat && ok) {  // statistics of the stored (bf16-rounded) values
+            bool st_ok;
+            if constexpr (RAG) st_ok = stat && ok && t < Tin;
+            else st_ok = stat && ok;
+            if (st_ok) {  // statistics of the stored (bf16-rounded) values
                 float f[8];
                 unpack8(o, f);
 #pragma unroll
@@ -472,9 +492,9 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
 #endif
 }
 
-template <int PACT, bool HR, bool HA, int KS, int NCH, bool AL, int WPW = 1, int BT = 128>
+template <int PACT, bool HR, bool HA, int KS, int NCH, bool AL, int WPW = 1, int BT = 128, bool RAG = false>
 __global__ __launch_bounds__(NTH, NCH == 1 ? STZS_MRFV_OCC1 : STZS_MRFV_OCC) void mrfv_conv(const stzs_conv_args a) {
-    mrfv_body<PACT, HR, HA, KS, NCH, AL, WPW, BT>(a);
+    mrfv_body<PACT, HR, HA, KS, NCH, AL, WPW, BT, RAG>(a);
 }
 
 // (r06) the three resblocks' convs of one MRF layer (k 3 / 7 / 11, same input, same shape and form) in ONE launch: grid

@@ -26,7 +26,9 @@ __global__ __launch_bounds__(256) void chan_stats_partial(const stzs_stats_args 
     float s[8], q[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
-    const int r0 = chunk * STAT_ROWS, r1 = min(a.T, r0 + STAT_ROWS);
+    // ragged frame batch: rows below this utterance's own count only (a chunk wholly past it: zero partials)
+    const int Tb = a.lens ? rag_rows(a.lens, b, a.lens_mul, a.T) : a.T;
+    const int r0 = chunk * STAT_ROWS, r1 = min(Tb, r0 + STAT_ROWS);
     const T* X = reinterpret_cast<const T*>(a.x) + (long)b * a.bs;
     if (c < a.C) {
         // four rows' 16-B loads in flight per pass, accumulated in row order (same sums as one row at a time)
@@ -114,7 +116,9 @@ STZS_DEV void stats_final_body(const stzs_stats_args a, int nchunk, int b, int b
             q += red[y][tid][1];
         }
         float mu, rs;
-        stat_finish(s, q, a.T, a.eps, mu, rs);  // (common.hpp: the same rounding as the conv prologue's pro_part path)
+        // (ragged frame batch: the chunks past the utterance's own rows added exact zeros; divide by its own count)
+        const int Tb = a.lens ? rag_rows(a.lens, b, a.lens_mul, a.T) : a.T;
+        stat_finish(s, q, Tb, a.eps, mu, rs);  // (common.hpp: the same rounding as the conv prologue's pro_part path)
         a.mean[(long)b * a.stat_bs + c] = mu;
         a.rstd[(long)b * a.stat_bs + c] = rs;
     }

@@ -114,6 +114,12 @@ __global__ __launch_bounds__(256) void dwup_kernel(const stzs_dwup_args a) {
     const bool odd = to & 1;
     const T* X = reinterpret_cast<const T*>(a.x) + (long)b * a.bsx;
     T* Y = reinterpret_cast<T*>(a.y) + (long)b * a.bsy + (long)to * a.ldy;
+    // ragged frame batch: this utterance's own input rows (clamped into [1, T]; uniform per workgroup)
+    const int Tb = a.lens ? rag_rows(a.lens, b, 1, a.T) : a.T;
+    if (m >= Tb) {  // an output row past 2 T_b: exact zeros, no input row read
+        for (int c = threadIdx.x; c < a.C; c += 256) DT<T>::st(Y + c, 0.f);
+        return;
+    }
     for (int c = threadIdx.x; c < a.C; c += 256) {
         const float mu = a.mean[(long)b * a.stat_bs + c], rs = a.rstd[(long)b * a.stat_bs + c];
         const float g = a.gb[(long)b * a.gb_bs + c], be = a.gb[(long)b * a.gb_bs + a.gb_beta_off + c];
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(256) void dwup_kernel(const stzs_dwup_args a) {
             o = v0 * a.w[c * 3 + 1];
         } else {
             float v1 = 0.f;
-            if (m + 1 < a.T) {
+            if (m + 1 < Tb) {
                 v1 = DT<T>::ld(X + (long)(m + 1) * a.ldx + c) * sc + sh;
                 v1 = v1 >= 0.f ? v1 : v1 * a.slope;
             }

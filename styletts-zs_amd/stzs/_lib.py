@@ -37,6 +37,14 @@ i32 = C.c_int32
 f32 = C.c_float
 
 
+class opt_vp(C.c_void_p):
+    """an OPTIONAL pointer field (NULL = the call as it was before the field existed): the same 8 bytes as a
+    c_void_p, assigned like one (an address or None; read back through .value), kept apart by its type -- a loop
+    over a struct's required pointers (tests/test_precise_frontend_host.py) does not take it for one, and
+    tools/launch_trace.py records it only when it is set, so a trace of calls that leave it NULL is the trace from
+    before the field.  The ragged-reference fields are declared with it."""
+
+
 class ConvArgs(C.Structure):
     _fields_ = [(n, vp) for n in ("x", "w", "bias", "y", "res", "acc_in", "gate", "pro_mean", "pro_rstd",
                                   "pro_gb", "pro_alpha")] + \
@@ -48,13 +56,15 @@ class ConvArgs(C.Structure):
                [(n, f32) for n in ("pro_cscale", "pro_slope", "epi_slope", "alpha", "beta", "pad_f")] + \
                [("stat_part", vp), ("stat_ld", i64), ("x_scale", vp), ("w_scale", vp),
                 ("splitk_ws", vp), ("splitk_ctr", vp), ("splitk", i32), ("pad_sk", i32),
-                ("pro_part", vp), ("pro_ld", i64), ("pro_nch", i32), ("pro_T", i32), ("pro_eps", f32), ("pad_pp", f32)]
+                ("pro_part", vp), ("pro_ld", i64), ("pro_nch", i32), ("pro_T", i32), ("pro_eps", f32), ("pad_pp", f32),
+                ("t_lens", opt_vp), ("t_lens_mul", i32), ("pad_tl", i32)]  # ragged frame batch: rows per utterance
 
 
 class StatsArgs(C.Structure):
     _fields_ = [("x", vp), ("mean", vp), ("rstd", vp), ("partial", vp),
                 ("ld", i64), ("bs", i64), ("stat_bs", i64),
-                ("B", i32), ("T", i32), ("C", i32), ("dtype", i32), ("eps", f32), ("pad_f", f32)]
+                ("B", i32), ("T", i32), ("C", i32), ("dtype", i32), ("eps", f32), ("pad_f", f32),
+                ("lens", opt_vp), ("lens_mul", i32), ("pad_l", i32)]  # ragged frame batch: rows per utterance
 
 
 class RowLNArgs(C.Structure):
@@ -111,7 +121,8 @@ class GatherArgs(C.Structure):
 class DwupArgs(C.Structure):
     _fields_ = [(n, vp) for n in ("x", "y", "mean", "rstd", "gb", "w", "wb")] + \
                [(n, i64) for n in ("ldx", "bsx", "ldy", "bsy", "stat_bs", "gb_bs", "gb_beta_off")] + \
-               [("B", i32), ("T", i32), ("C", i32), ("dtype", i32), ("slope", f32), ("pad_f", f32)]
+               [("B", i32), ("T", i32), ("C", i32), ("dtype", i32), ("slope", f32), ("pad_f", f32),
+                ("lens", opt_vp)]  # ragged frame batch: input rows per utterance
 
 
 class F0nArgs(C.Structure):
@@ -137,14 +148,6 @@ class IstftStreamArgs(C.Structure):
     _fields_ = [("post", vp), ("tail_in", vp), ("tail_out", vp), ("wav", vp),
                 ("ldp", i64), ("bsp", i64), ("bsw", i64), ("ldt", i64),
                 ("B", i32), ("f0", i32), ("Fc", i32), ("final_chunk", i32), ("n_fft", i32), ("hop_s", i32)]
-
-
-class opt_vp(C.c_void_p):
-    """an OPTIONAL pointer field (NULL = the call as it was before the field existed): the same 8 bytes as a
-    c_void_p, assigned like one (an address or None; read back through .value), kept apart by its type -- a loop
-    over a struct's required pointers (tests/test_precise_frontend_host.py) does not take it for one, and
-    tools/launch_trace.py records it only when it is set, so a trace of calls that leave it NULL is the trace from
-    before the field.  The ragged-reference fields are declared with it."""
 
 
 class FramesArgs(C.Structure):

@@ -268,14 +268,17 @@ class _StatsRef:
     in `part`, finalised into mean / rstd (stzs_chan_stats_final) only when something needs them: a generic-path
     conv reads the partials in its AdaIN prologue instead (stzs_conv_args.pro_part, the same bits)."""
 
-    def __init__(self, eng, part, ld, nch, T, B, mean, rstd, chunk_rows):
+    def __init__(self, eng, part, ld, nch, T, B, mean, rstd, chunk_rows, lens=None, lens_mul=1):
         self.eng, self.part, self.ld, self.nch, self.T, self.B = eng, part, ld, nch, T, B
         self.mean, self.rstd, self.chunk_rows, self.done = mean, rstd, chunk_rows, False
+        self.lens, self.lens_mul = lens, lens_mul  # ragged frames: the rows each utterance's partials cover
 
     def final_args(self, s):
         """fill s (stzs_stats_args) for the finalise of these partials -> s"""
         s.mean, s.rstd, s.partial = self.mean.data_ptr(), self.rstd.data_ptr(), self.part.data_ptr()
         s.stat_bs, s.B, s.T, s.C, s.eps = self.ld, self.B, self.T, self.ld, 1e-5
+        if self.lens is not None:
+            s.lens, s.lens_mul = self.lens.data_ptr(), self.lens_mul
         return s
 
     def finalize(self):
@@ -482,7 +485,7 @@ class StyleTTSZS:
              pro_slope=0.0, pro_alpha=None, cscale=1.0, res: Act = None, res_tdiv=1, acc_in: Act = None,
              alpha=1.0, beta=0.0, gate=None, gate_bs=0, epi_act=L.ACT_NONE, epi_slope=0.0, ups_pad=0,
              T_final=0, refl=0, flags=0, stats_key=None, x_scale=None, post_ln=None, pre_ln=None, splitk=0, rows=0,
-             attn=None, collect=None, what="conv"):
+             attn=None, collect=None, t_lens=None, t_lens_mul=1, what="conv"):
         """-> y, or (y, (mean, rstd, stat_bs)) with stats_key: InstanceNorm statistics of the stored
         output fused into the conv epilogue (per-tile partials) + one small finalize launch.
         collect (a list): append the conv's stzs_conv_args to it instead of launching (the caller launches the
@@ -492,18 +495,24 @@ class StyleTTSZS:
         behind the linear.  (r03 also ran them, and the sampler's CFG + Euler step, inside the small-M linear's launch
         by its last-arriving workgroups: bit-identical but slower at batch 1, removed in r04 -- DESIGN.md §5.)
         pre_ln (stzs_rowln_args): the LayerNorm whose output x is, launched before the linear -- or, on the small-M
-        rows form, fused into it (stzs_ln_linear, csrc/lnrows.hip: the normalised rows never leave the chip)."""
+        rows form, fused into it (stzs_ln_linear, csrc/lnrows.hip: the normalised rows never leave the chip).
+        t_lens (int32 [B] device tensor, ragged frames): utterance b holds t_lens[b] * t_lens_mul rows
+        (stzs_conv_args.t_lens; the library refuses the forms that do not honour it); its fused statistics are
+        finalised here with the same lengths, never deferred."""
         a, pro_ref = self._conv_fill(cw, x, y, what, T_out=T_out, pad=pad, dil=dil, stride=stride, pro=pro,
                                      pro_act=pro_act, pro_slope=pro_slope, pro_alpha=pro_alpha, cscale=cscale, res=res,
                                      res_tdiv=res_tdiv, acc_in=acc_in, alpha=alpha, beta=beta, gate=gate,
                                      gate_bs=gate_bs, epi_act=epi_act, epi_slope=epi_slope, ups_pad=ups_pad,
                                      T_final=T_final, refl=refl, x_scale=x_scale)
         rows = self._conv_route(a, cw, x, y, flags, rows, cscale, res, stats_key)
+        if t_lens is not None:
+            assert collect is None and pro_ref is None and splitk <= 1 and rows == 0, what
+            a.t_lens, a.t_lens_mul = t_lens.data_ptr(), t_lens_mul
         if rows > 1 or splitk > 1:
             self._conv_splitk(a, cw, x, splitk, rows, collect, what)
         if pro_ref is not None:
             self._conv_stats_in(a, cw, pro_ref, pre_ln)
-        st = self._conv_stats_out(a, cw, y, stats_key, collect) if stats_key is not None else None
+        st = self._conv_stats_out(a, cw, y, stats_key, collect, t_lens is not None) if stats_key is not None else None
         fn, args, fused = self._conv_entry(a, cw, x, res, res_tdiv, gate, pre_ln, st)
         if collect is not None:
             assert len(args) == 1 and pre_ln is None and post_ln is None and attn is None, what
@@ -523,7 +532,7 @@ class StyleTTSZS:
         if st is None:
             return y
         slab, Cc, mean, rstd, defer, ntile = st
-        ref = _StatsRef(self, slab, Cc, ntile, a.T_out, y.B, mean, rstd, L.CONV_STAT_ROWS)
+        ref = _StatsRef(self, slab, Cc, ntile, a.T_out, y.B, mean, rstd, L.CONV_STAT_ROWS, t_lens, t_lens_mul)
         if not defer:
             ref.finalize()
             return y, (mean, rstd, Cc)
@@ -668,12 +677,12 @@ class StyleTTSZS:
         else:
             a.pro_mean, a.pro_rstd = pro_ref.mean_ptr(), pro_ref.rstd_ptr()
 
-    def _conv_stats_out(self, a, cw, y, stats_key, collect):
+    def _conv_stats_out(self, a, cw, y, stats_key, collect, ragged=False):
         """conv() step 5: the slab the epilogue writes the output's statistics partials to, and their mean / rstd
         buffers -> (slab, channels, mean, rstd, finalise deferred?, partial chunks)"""
         Cc = _rup(cw.Co, 8)
         ntile = (a.T_out + L.CONV_STAT_ROWS - 1) // L.CONV_STAT_ROWS
-        defer = collect is not None or (self.defer_stats and ntile <= 8)
+        defer = (collect is not None or (self.defer_stats and ntile <= 8)) and not ragged
         # (deferred: the partials must outlive this launch until their consumer reads them -- a slab per key)
         slab = self._scratch("stat_slab." + stats_key, y.B * ntile * Cc * 2, 1024) if defer else \
             self._scratch("stat_slab", y.B * ntile * Cc * 2)
@@ -795,19 +804,23 @@ class StyleTTSZS:
         torch.cuda.synchronize(self.device)
         return [(w, e0.elapsed_time(e1) * 1e-3, f, b, shp, stg) for (w, e0, e1, f, b, shp, stg) in tm["rec"]]
 
-    def stats(self, x: Act, key):
+    def stats(self, x: Act, key, lens=None, lens_mul=1):
         """InstanceNorm statistics of x over time -> (mean, rstd, stat_bs); with defer_stats and <= 8 256-row chunks
-        only the partials pass runs here (the consuming conv's prologue, or the first other use, finalises)."""
+        only the partials pass runs here (the consuming conv's prologue, or the first other use, finalises).
+        lens (int32 [B] device tensor, ragged frames): over utterance b's first lens[b] * lens_mul rows, finalised
+        here."""
         Cc = _rup(x.C, 8)
         mean = self.buf(key + ".m", (x.B, Cc), torch.float32)
         rstd = self.buf(key + ".r", (x.B, Cc), torch.float32)
         nch = (x.T + 255) // 256
-        defer = self.defer_stats and nch <= 8
+        defer = self.defer_stats and nch <= 8 and lens is None
         nws = self.lib.stzs_chan_stats_workspace(x.B, x.T, Cc) // 4 + 1
         ws = self._scratch("stat_ws." + key, nws, 1024) if defer else self._scratch("stat_ws", nws)
         a = L.StatsArgs()
         a.x, a.mean, a.rstd, a.partial = x.ptr, mean.data_ptr(), rstd.data_ptr(), ws.data_ptr()
         a.ld, a.bs, a.stat_bs, a.B, a.T, a.C, a.dtype, a.eps = x.ld, x.bs, Cc, x.B, x.T, Cc, x.dt, 1e-5
+        if lens is not None:
+            a.lens, a.lens_mul = lens.data_ptr(), lens_mul
         cost = (0, x.B * x.T * x.C * x.t.element_size())
         if not defer:
             self._call(self.lib.stzs_chan_stats, a, "chan_stats", cost=cost)
@@ -1313,11 +1326,17 @@ class StyleTTSZS:
         self.conv(cw, x, view, T_out=T, what=what)
 
     # ------------------------------------------------------------------ (b) prosody predictor
-    def predict_prosody(self, h_txt: Act, codes: torch.Tensor, durations=None, n_frames=None, text_lens=None):
+    def predict_prosody(self, h_txt: Act, codes: torch.Tensor, durations=None, n_frames=None, text_lens=None,
+                        ragged_frames=False):
         """durations: optional int tensor [B, T_txt] (host or device); n_frames: their per-utterance sum if
         known (avoids the device->host sync, e.g. under graph capture).  Returns dict of device tensors.
         text_lens: ragged text rows (duration_encoder); the padding tokens get duration 0 and the alignment never
-        references them, so the batch still only has to share its frame count."""
+        references them, so the batch still only has to share its frame count.
+        ragged_frames: the rows need not share their frame count: the batch runs at the padded width T40 = the
+        longest row's (or n_frames, then the padded width: no host sync at all), each row on its own frames
+        (prosody_frames; the result gains "frame_lens")."""
+        if ragged_frames:
+            self._check_ragged_frames()
         text_lens = self.text_lens(text_lens, h_txt.B, h_txt.T)
         if self.dur_overlap and durations is not None and (n_frames is not None or durations.device.type == "cpu"):
             # the alignment reads the given durations, so the duration LSTM no longer gates the frame branch: it
@@ -1331,12 +1350,13 @@ class StyleTTSZS:
                 if text_lens is not None:  # (forced durations of padding tokens do not count: the kernel zeroes them)
                     tot = tot * (torch.arange(h_txt.T)[None] < text_lens.cpu()[:, None])
                 tot = tot.sum(1)
-                assert int(tot.min()) == int(tot.max()), \
+                assert ragged_frames or int(tot.min()) == int(tot.max()), \
                     "one batch must share its total frame count (stzs.scheduler.BucketScheduler groups by it)"
-                T40 = int(tot[0])
+                T40 = int(tot.max())
             if text_lens is not None:  # the alignment reads the durations with the padding tokens' zeroed
                 ov = self._mask_durations(ov, text_lens)
-            pro = self.prosody_frames(h_txt, codes, d, ov, T40, pair_dur=True, text_lens=text_lens)
+            pro = self.prosody_frames(h_txt, codes, d, ov, T40, pair_dur=True, text_lens=text_lens,
+                                      ragged_frames=ragged_frames)
             du = self.duration_head(d, ov, hd=pro.pop("_hd"), text_lens=text_lens)
             pro.update(du, dur=du["dur"])
             return pro
@@ -1348,10 +1368,30 @@ class StyleTTSZS:
                 tot = durations.to(torch.int64).sum(1)
             else:
                 tot = du["dur"].to(torch.int64).sum(1).cpu()  # host sync: the frame count sizes every later buffer
-            assert int(tot.min()) == int(tot.max()), \
+            assert ragged_frames or int(tot.min()) == int(tot.max()), \
                 "one batch must share its total frame count (stzs.scheduler.BucketScheduler groups by it)"
-            T40 = int(tot[0])
-        return self.prosody_frames(h_txt, codes, du["d"], du["dur"], T40, du)
+            T40 = int(tot.max())
+        return self.prosody_frames(h_txt, codes, du["d"], du["dur"], T40, du, ragged_frames=ragged_frames)
+
+    def _check_ragged_frames(self):
+        """ragged frames run on the default engine's conv forms only: the latency engine's split-K / pair convs and
+        the precise engines' conv_x3 / mrfx forms do not take the lengths (before any launch)"""
+        if self.blk_splitk or self.precise or self.precise_all:
+            raise NotImplementedError("ragged_frames: the default engine only (not blk_splitk / precise engines)")
+
+    def prosody_rows(self, pro: dict, rows, T_b: int) -> dict:
+        """rows (indices) of a ragged-frames result that share the frame count T_b -> a pro dict decode() accepts for
+        them: asr_buf[b, :T_b, :d_txt], F0[b, :2 T_b] and N[b, :2 T_b] copied into fresh buffers (data movement only;
+        the source may be overwritten by the next prosody batch, and decode() fills the copy's F0 / N columns)."""
+        S = self.spec
+        T_b = int(T_b)
+        assert 1 <= T_b <= pro["T40"], (T_b, pro["T40"])
+        ix = torch.as_tensor(list(rows), dtype=torch.int64, device=self.device)
+        src = pro["asr_buf"]
+        asr = torch.zeros(len(ix), T_b, src.t.shape[2], dtype=src.t.dtype, device=self.device)
+        asr[:, :, :S.d_txt] = src.t[ix, :T_b, src.c0:src.c0 + S.d_txt]
+        return dict(asr_buf=Act(asr, 0, S.d_txt + 2), F0=pro["F0"][ix, :2 * T_b].contiguous(),
+                    N=pro["N"][ix, :2 * T_b].contiguous(), T40=T_b)
 
     def predict_durations(self, h_txt: Act, codes: torch.Tensor, durations=None, text_lens=None) -> dict:
         """a5-a6: DurationEncoder + duration LSTM + head -> dict(dur int32 [B, T], dsum, logits, d) (device).
@@ -1442,10 +1482,17 @@ class StyleTTSZS:
         return dict(dur=dur, dsum=dsum, logits=logits, d=d)
 
     def prosody_frames(self, h_txt: Act, codes: torch.Tensor, d: Act, dur: torch.Tensor, T40: int,
-                       extra: dict = None, pair_dur=False, text_lens=None) -> dict:
+                       extra: dict = None, pair_dur=False, text_lens=None, ragged_frames=False) -> dict:
         """a7-a8 for a batch sharing T40 aligned frames: alignment, gathers, shared LSTM, F0 / N curves.
         pair_dur: the duration LSTM over d runs in the shared LSTM's launch (its output as "_hd"), with the rows'
-        text_lens when the text is ragged (the frames are not: one T40)."""
+        text_lens when the text is ragged (the frames are not: one T40).
+        ragged_frames: T40 is the padded width and row b holds its own frame count, the sum of its durations -- the
+        alignment's total[b], read on the device by every later kernel (no host sync), returned as "frame_lens".
+        Row b's idx / en / aligned text rows / F0[b, :2 T_b] / N[b, :2 T_b] are those of the row alone at T40 = T_b;
+        past it idx is -1, en and the aligned text rows are zeros, F0 / N finite and unspecified (prosody_rows cuts
+        the rows of one frame count out for decode()).  The default engine only (NotImplementedError otherwise)."""
+        if ragged_frames:
+            self._check_ragged_frames()
         S, W = self.spec, self.W
         B, T = h_txt.B, h_txt.T
         pin = S.pr_in
@@ -1465,22 +1512,33 @@ class StyleTTSZS:
             self.gather(h_txt, idx, enc_in, S.d_txt)
         hd = self.act("pr.hd", B, T, S.pr_hid, self.adt) if pair_dur else None
         F0, Nn = self.f0n_predictor(en, codes,
-                                    dur_rec=(W.pr_dur_lstm, d, hd, "pr.dur_lstm", text_lens) if pair_dur else None)
+                                    dur_rec=(W.pr_dur_lstm, d, hd, "pr.dur_lstm", text_lens) if pair_dur else None,
+                                    frame_lens=total if ragged_frames else None)
         out = dict(extra or {}, dur=dur, idx=idx, T40=T40, en=en, asr_buf=enc_in, d=d, F0=F0, N=Nn)
+        if ragged_frames:
+            out["frame_lens"] = total
         if pair_dur:
             out["_hd"] = hd
         return out
 
-    def f0n_predictor(self, en: Act, codes: torch.Tensor, dur_rec=None):
+    def f0n_predictor(self, en: Act, codes: torch.Tensor, dur_rec=None, frame_lens=None):
         """a8: shared BiLSTM over the aligned frames, then per branch (F0, N) three AdaIN residual blocks (the
-        middle one x2 upsampling) and a 1x1 projection.  en [B, T40, pr_in] bf16 -> F0, N fp32 [B, 2 T40]."""
+        middle one x2 upsampling) and a 1x1 projection.  en [B, T40, pr_in] bf16 -> F0, N fp32 [B, 2 T40].
+        frame_lens (int32 [B] device tensor, ragged frames): row b holds frame_lens[b] frames of the T40; the LSTM
+        resets at its end, statistics / block convs / upsampling take the lengths (stzs_conv_args.t_lens, ...), so
+        F0[b, :2 frame_lens[b]] and N likewise are those of the row alone; past it they are finite, unspecified.
+        Statistics are finalised where they are produced (no pro_part, no deferral): the shared xs statistics are
+        complete on the current stream before the F0 || N fork."""
+        fl = frame_lens
+        if fl is not None:
+            self._check_ragged_frames()
         S, W = self.spec, self.W
         B, T40 = en.B, en.T
         xs = self.act("pr.xs", B, T40, S.pr_hid, self.adt)
         if dur_rec is None:
-            self.lstm(W.pr_shared, en, xs, "pr.shared")
+            self.lstm(W.pr_shared, en, xs, "pr.shared", lens=fl)
         else:  # dur_rec = (lw, x, y, key, text_lens | None): the duration LSTM beside it, one launch
-            self.lstm_pair((W.pr_shared, en, xs, "pr.shared"), dur_rec)
+            self.lstm_pair((W.pr_shared, en, xs, "pr.shared", fl), dur_rec)
         sg = self.mean_rows(codes, S.style_ac, S.style_pr, "pr.sg")
         ng = W.pr_norm
         gbp = self.buf("pr.gbn", (B, ng.total), torch.float32)
@@ -1490,7 +1548,7 @@ class StyleTTSZS:
         Nn = self.buf("pr.N", (B, T80, 1), torch.float32)
         c0, c1, c2 = S.f0n_ch
 
-        s0 = self.stats(xs, "pr.xs.s1")  # (both branches' first AdaIN normalise xs: its statistics once, r06)
+        s0 = self.stats(xs, "pr.xs.s1", fl)  # (both branches' first AdaIN normalise xs: its statistics once, r06)
         if self.f0n_pair and self.blk_splitk and not self._fork_on("f0n"):
             # (r06) the two branches in lockstep, each block's two convs of both branches as one launch pair
             # (stzs_conv1d_group -> conv_mfma_pair / splitk_epi_pair): same bits as branch after branch
@@ -1509,9 +1567,9 @@ class StyleTTSZS:
             y0 = self.act(f"pr.{br}.y0", B, T40, c0, self.adt)
             y1 = self.act(f"pr.{br}.y1", B, T80, c1, self.adt)
             y2 = self.act(f"pr.{br}.y2", B, T80, c2, self.adt)
-            self.blk(W.pr_blk[f"pr.{br}0"], xs, y0, ng, gbp, f"pr.{br}0", self.adt, s1=s0)
-            self.blk(W.pr_blk[f"pr.{br}1"], y0, y1, ng, gbp, f"pr.{br}1", self.adt)
-            self.blk(W.pr_blk[f"pr.{br}2"], y1, y2, ng, gbp, f"pr.{br}2", self.adt)
+            self.blk(W.pr_blk[f"pr.{br}0"], xs, y0, ng, gbp, f"pr.{br}0", self.adt, s1=s0, flens=fl)
+            self.blk(W.pr_blk[f"pr.{br}1"], y0, y1, ng, gbp, f"pr.{br}1", self.adt, flens=fl)
+            self.blk(W.pr_blk[f"pr.{br}2"], y1, y2, ng, gbp, f"pr.{br}2", self.adt, flens=fl, fmul=2)
             self.conv(W.pr_blk[f"pr.{br}_proj"], y2, Act(out, 0, 1), what=f"pr.{br}_proj")
         self.fork("f0n", lambda: branch("f0", F0), lambda: branch("n", Nn))
         return F0[:, :, 0], Nn[:, :, 0]
@@ -1523,12 +1581,16 @@ class StyleTTSZS:
         a.B, a.Tsrc, a.Tdst, a.C, a.xc0, a.yc0, a.dtype = x.B, x.T, y.T, Cn, x.c0, y.c0, x.dt
         self._call(self.lib.stzs_gather_rows, a, "gather")
 
-    def blk(self, bw, x: Act, out: Act, ng, gb: torch.Tensor, key, dt=torch.bfloat16, s1=None):
+    def blk(self, bw, x: Act, out: Act, ng, gb: torch.Tensor, key, dt=torch.bfloat16, s1=None, flens=None, fmul=1):
         """AdainResBlk1d: out = (conv2(act(AdaIN(conv1(up(act(AdaIN(x))))))) + sc(x)) / sqrt 2.
-        s1: x's statistics when the caller already has them (self.stats(x, ...))."""
-        s1 = s1 if s1 is not None else self.stats(x, key + ".s1")
-        r, s2 = self._blk_conv1(bw, x, s1, ng, gb, key, dt)
-        self._blk_conv2(bw, r, s2, self._blk_shortcut(bw, x, key, dt), out, ng, gb, key, dt)
+        s1: x's statistics when the caller already has them (self.stats(x, ...)).
+        flens (int32 [B] device tensor, ragged frames): utterance b's x holds flens[b] * fmul rows (fmul 2 behind the
+        upsampling block); statistics, the k3 convs and the upsampling take the lengths, the 1x1 shortcut needs none
+        (its rows past an utterance's end are never read as a residual)."""
+        s1 = s1 if s1 is not None else self.stats(x, key + ".s1", flens, fmul)
+        r, s2 = self._blk_conv1(bw, x, s1, ng, gb, key, dt, flens=flens, fmul=fmul)
+        self._blk_conv2(bw, r, s2, self._blk_shortcut(bw, x, key, dt), out, ng, gb, key, dt, flens=flens,
+                        fmul=2 if bw.up else fmul)
         return out
 
     def _blk_pair(self, items, ng, gb: torch.Tensor, dt):
@@ -1556,7 +1618,7 @@ class StyleTTSZS:
         return pick(bw.conv1s, bw.conv1), pick(bw.conv2s, bw.conv2), \
             (None if bw.sc is None else pick(bw.scs, bw.sc)), sk
 
-    def _blk_conv1(self, bw, x: Act, s1, ng, gb: torch.Tensor, key, dt, collect=None):
+    def _blk_conv1(self, bw, x: Act, s1, ng, gb: torch.Tensor, key, dt, collect=None, flens=None, fmul=1):
         """a block's conv1 over act(AdaIN(x)) -- in an upsampling block over the x2 depthwise ConvTranspose of it
         (stzs_adain_dwup) -- with its output's statistics fused -> (r, (mean, rstd, stat_bs) of r)"""
         c1, _, _, sk = self._blk_weights(bw, dt)
@@ -1566,6 +1628,9 @@ class StyleTTSZS:
         To = 2 * x.T if bw.up else x.T
         r = self.act(key + ".r", x.B, To, bw.dout, dt)
         kw = dict(pad=1, stats_key=key + ".s2", splitk=sk, collect=collect, what=key + ".conv1")
+        if flens is not None:  # (conv1 of an upsampling block reads the doubled rows)
+            assert not (bw.up and fmul != 1), key
+            kw.update(t_lens=flens, t_lens_mul=2 if bw.up else fmul)
         if not bw.up:
             return r, self.conv(c1, x, r, pro=(m1, r1, sb1, gb1, gbs, n1), pro_act=L.ACT_LEAKY, pro_slope=0.2, **kw)[1]
         u = self.act(key + ".u", x.B, To, bw.din, dt)
@@ -1574,6 +1639,7 @@ class StyleTTSZS:
         a.w, a.wb = self.W.t(bw.pool_w).data_ptr(), self.W.t(bw.pool_b).data_ptr()
         a.ldx, a.bsx, a.ldy, a.bsy, a.stat_bs, a.gb_bs, a.gb_beta_off = x.ld, x.bs, u.ld, u.bs, sb1, gbs, n1
         a.B, a.T, a.C, a.slope, a.dtype = x.B, x.T, bw.din, 0.2, x.dt
+        a.lens = flens.data_ptr() if flens is not None else None
         self._call(self.lib.stzs_adain_dwup, a, key + ".dwup")
         return r, self.conv(c1, u, r, **kw)[1]
 
@@ -1585,14 +1651,15 @@ class StyleTTSZS:
         scb = self.act(key + ".sc", x.B, x.T, bw.dout, dt)
         return self.conv(sc, x, scb, splitk=sk, what=key + ".sc")
 
-    def _blk_conv2(self, bw, r: Act, s2, res: Act, out: Act, ng, gb: torch.Tensor, key, dt, collect=None):
+    def _blk_conv2(self, bw, r: Act, s2, res: Act, out: Act, ng, gb: torch.Tensor, key, dt, collect=None, flens=None,
+                   fmul=1):
         """a block's conv2 over act(AdaIN(r)), plus the residual, / sqrt 2 -> out"""
         _, c2, _, sk = self._blk_weights(bw, dt)
         m2, r2, sb2 = s2
         off2, n2 = ng.offsets[bw.name + ".norm2"]
         self.conv(c2, r, out, pad=1, pro=(m2, r2, sb2, gb.data_ptr() + off2 * 4, ng.total, n2), pro_act=L.ACT_LEAKY,
                   pro_slope=0.2, res=res, res_tdiv=2 if bw.up else 1, alpha=1.0 / math.sqrt(2.0), splitk=sk,
-                  collect=collect, what=key + ".conv2")
+                  collect=collect, what=key + ".conv2", **({} if flens is None else dict(t_lens=flens, t_lens_mul=fmul)))
 
     # ------------------------------------------------------------------ (c) decoder
     def decode(self, pro: dict, codes: torch.Tensor, seeds, istft=True) -> torch.Tensor:

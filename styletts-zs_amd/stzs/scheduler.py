@@ -28,6 +28,13 @@ computed as alone on its first ref_lens[b] samples, the padding is never read: D
 key is (forced,) alone -- phase 1 is one batch per max_batch requests on any traffic; with both off the schedule is,
 call for call, the uniform one.  The padded block is as wide as the chunk's longest reference: the share of it that
 is padding is work this design accepts (requests are not sorted by reference length inside a chunk).
+
+ragged_frames=True (off by default) splits phase 2: phase 2a runs alignment and prosody (a7-a8) for chunks of <=
+max_batch requests in request order, whatever their frame counts -- text padded to the chunk's longest, ONE ragged
+batch per chunk at the padded width of its longest row (the engine's ragged_frames: row b is computed as alone on its
+own T_b frames); phase 2b groups by T40 as before, cuts each bucket's rows out of the prosody results
+(engine.prosody_rows: data movement only) and runs the decoder per bucket.  With it off the schedule is, call for
+call, the present one.
 """
 from __future__ import annotations
 
@@ -52,9 +59,11 @@ class Request:
 
 class BucketScheduler:
     def __init__(self, engine: StyleTTSZS, max_batch: int = 64, steps: int = 2, cfg_scale: float = 5.0,
-                 ragged_text: bool = False, ragged_ref: bool = False):
+                 ragged_text: bool = False, ragged_ref: bool = False, ragged_frames: bool = False):
+        if ragged_frames:
+            engine._check_ragged_frames()  # (NotImplementedError on the latency / precise engines, before any launch)
         self.eng, self.max_batch, self.steps, self.cfg = engine, max_batch, steps, cfg_scale
-        self.ragged_text, self.ragged_ref = ragged_text, ragged_ref
+        self.ragged_text, self.ragged_ref, self.ragged_frames = ragged_text, ragged_ref, bool(ragged_frames)
         self.stats = {}
 
     def _chunks(self, ids):
@@ -75,6 +84,59 @@ class BucketScheduler:
                 key = (int(r.tokens.shape[0]),) + key
             g1.setdefault(key, []).append(i)
         return [(key[-1], ch) for key, ids in g1.items() for ch in self._chunks(ids)]
+
+    def phase2_groups(self, frames: List[int]):
+        """the phase-2 batches for the requests' frame counts, in launch order -> (prosody batches, decoder batches),
+        each a list of request-index lists of at most max_batch.  Without ragged_frames a batch shares its T40 and
+        runs prosody and decoder together (the two lists are the same); with it the prosody batches are chunks of the
+        requests in request order and only the decoder batches share a T40.  Pure host bookkeeping."""
+        g2 = OrderedDict()
+        for i, n in enumerate(frames):
+            g2.setdefault(int(n), []).append(i)
+        dec = [ch for ids in g2.values() for ch in self._chunks(ids)]
+        if not self.ragged_frames:
+            return dec, dec
+        return list(self._chunks(list(range(len(frames))))), dec
+
+    def _phase2_inputs(self, per, ch):
+        """the padded text rows / duration-encoder rows / durations and the codes of requests ch"""
+        dev = self.eng.device
+        Tm = max(per[i]["h"].shape[0] for i in ch)
+        b = len(ch)
+        h = torch.zeros(b, Tm, per[ch[0]]["h"].shape[1], dtype=per[ch[0]]["h"].dtype, device=dev)
+        d = torch.zeros(b, Tm, per[ch[0]]["d"].shape[1], dtype=per[ch[0]]["d"].dtype, device=dev)
+        dur = torch.zeros(b, Tm, dtype=torch.int32, device=dev)
+        for j, i in enumerate(ch):
+            T = per[i]["h"].shape[0]
+            h[j, :T], d[j, :T], dur[j, :T] = per[i]["h"], per[i]["d"], per[i]["dur"]
+        codes = torch.stack([per[i]["codes"] for i in ch]).contiguous()
+        return h, d, dur, codes
+
+    def _phase2_ragged(self, per, out):
+        """phase 2a (one ragged prosody batch per chunk of requests) and 2b (decoder per frame bucket)
+        -> (prosody batches, decoder batches, padded frame blocks, of them tail)"""
+        eng, S = self.eng, self.eng.spec
+        pros, dec = self.phase2_groups([p["T40"] for p in per])
+        fr_n = pad_n = 0
+        for ch in pros:
+            h, d, dur, codes = self._phase2_inputs(per, ch)
+            Tp = max(per[i]["T40"] for i in ch)
+            pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, Tp, ragged_frames=True)
+            fr_n += Tp * len(ch)
+            pad_n += Tp * len(ch) - sum(per[i]["T40"] for i in ch)
+            # each row's prosody cut out before the next chunk reuses the buffers (data movement only)
+            for j, i in enumerate(ch):
+                per[i]["pro"] = eng.prosody_rows(pro, [j], per[i]["T40"])
+        for ch in dec:
+            T40 = per[ch[0]]["T40"]
+            asr = torch.cat([per[i]["pro"]["asr_buf"].t for i in ch])
+            pro = dict(asr_buf=Act(asr, 0, S.d_txt + 2), F0=torch.cat([per[i]["pro"]["F0"] for i in ch]),
+                       N=torch.cat([per[i]["pro"]["N"] for i in ch]), T40=T40)
+            codes = torch.stack([per[i]["codes"] for i in ch]).contiguous()
+            wav = eng.decode(pro, codes, [per[i]["seed"] for i in ch])
+            for j, i in enumerate(ch):
+                out[i] = wav[j].clone()
+        return len(pros), len(dec), fr_n, pad_n
 
     def synth(self, reqs: List[Request]) -> List[torch.Tensor]:
         """-> one fp32 waveform [600 * T40_i] per request, in request order (device tensors)."""
@@ -136,7 +198,10 @@ class BucketScheduler:
             g2.setdefault(p["T40"], []).append(i)
         out = [None] * len(reqs)
         n2 = 0
-        for T40, ids in g2.items():
+        npro, fr_n, fpad_n = None, 0, 0
+        if self.ragged_frames:
+            npro, n2, fr_n, fpad_n = self._phase2_ragged(per, out)
+        for T40, ids in ([] if self.ragged_frames else g2.items()):
             for ch in self._chunks(ids):
                 n2 += 1
                 Tm = max(per[i]["h"].shape[0] for i in ch)
@@ -155,5 +220,8 @@ class BucketScheduler:
         eng.check_status()  # the phase-2 prosody LSTMs
         self.stats = dict(requests=len(reqs), phase1_batches=n1, phase2_batches=n2,
                           frame_buckets=sorted(g2.keys()), phase1_ms=1e3 * t1,
-                          ref_pad_share=pad_n / max(ref_n, 1))
+                          ref_pad_share=pad_n / max(ref_n, 1),
+                          # prosody batches (ragged_frames: fewer than the decoder's; else one per phase-2 batch) and
+                          # the share of the padded prosody frame blocks that is tail
+                          prosody_batches=n2 if npro is None else npro, frame_pad_share=fpad_n / max(fr_n, 1))
         return out

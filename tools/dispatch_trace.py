@@ -134,7 +134,7 @@ NONE, LEAKY, SNAKE, GELU, SILU = 0, 1, 2, 3, 4
 LANE16, NARROW32, WF32, LINEAR_IDS, FRAG32, X3, ROWS, UPS_NOISE = 16, 32, 64, 128, 256, 1024, 2048, 4096
 A_DMA, MRFV_NARROW, FRAG32X3, MRFV_T128, RING, SK_TICKET = 8, 8192, 16384, 32768, 65536, 131072  # include/stzs.h
 PTRS = ("x", "w", "bias", "y", "res", "acc_in", "gate", "pro_mean", "pro_rstd", "pro_gb", "pro_alpha", "stat_part",
-        "x_scale", "w_scale", "splitk_ws", "splitk_ctr", "pro_part")
+        "x_scale", "w_scale", "splitk_ws", "splitk_ctr", "pro_part", "t_lens")
 PTR = {n: 0x10000000 * (i + 1) for i, n in enumerate(PTRS)}  # fixed, 64-byte aligned, never dereferenced
 
 
@@ -369,6 +369,42 @@ def sweep_calls():
               ("in=i32", dict(in_dtype=I32)), ("G=NULL", dict(G=0)), ("Bt=NULL", dict(Bt=0)))
     for lab, ch in ln_bad:
         calls.append((f"lnlin.ln {lab}", "stzs_ln_linear", [conv(B=1, T=20, Ci=256, Co=200, x=0)], rowln(20, 256, F32, **ch)))
+    # ragged frame lengths (stzs_conv_args.t_lens): the generic conv_mfma path and the register-direct k3 block form
+    # launch their own instances ("tlens ..."); every other form or combination is refused before any runtime call
+    # ("tlens.bad ...": STZS_EINVAL, nothing launched)
+    TL = PTR["t_lens"]
+    for (i, pa, mul) in itertools.product((BF16, F32), (NONE, LEAKY), (0, 2)):
+        one(f"tlens mfma.k3 {i}{i} pa{pa} mul{mul}", conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, ind=i, outd=i, pro_act=pa, adain=True,
+                                                       stat=True, res=True, alpha=0.5, t_lens=TL, t_lens_mul=mul))
+    one("tlens mfma.k3 linear_ids", conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, flags=LINEAR_IDS, t_lens=TL))
+    for pa, r, ((B, T), fl) in itertools.product((NONE, LEAKY), (0, 1), (((2, 100), 0), ((2, 100), MRFV_T128), ((64, 1030), 0),
+                                                                    ((64, 1030), MRFV_NARROW))):
+        one(f"tlens frag32.blk pa{pa} r{r} B{B} T{T} f{fl}",
+            conv(B=B, T=T, Ci=512, Co=256, ks=3, cic=128, flags=FRAG32 | fl, pro_act=pa, res=bool(r), adain=True, stat=True,
+                 res_tdiv=1 + r, t_lens=TL, t_lens_mul=2 * r))
+    g3 = conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, adain=True, pro_act=LEAKY, t_lens=TL)
+    f3 = conv(B=4, T=200, Ci=256, Co=256, ks=3, cic=128, flags=FRAG32, adain=True, pro_act=LEAKY, t_lens=TL)
+    for lab, d in (("mfma snake", dict(g3, pro_act=SNAKE, pro_alpha=PTR["pro_alpha"])), ("mfma bf16->f32", dict(g3, out_dtype=F32)),
+                   ("mfma f32->bf16", dict(g3, in_dtype=F32)),
+                   ("mfma splitk", dict(g3, B=1, Ci=256, ci_pad=256, ldx=256, splitk=4, splitk_ws=PTR["splitk_ws"], splitk_ctr=PTR["splitk_ctr"])),
+                   ("mfma pro_part", dict(g3, pro_part=PTR["pro_part"], pro_nch=2, pro_T=200, pro_ld=64)),
+                   ("mfma stride 2", dict(g3, stride=2, T_out=100)), ("mfma T_out-1", dict(g3, T_out=199)),
+                   ("mfma ups", conv(Ci=256, Co=64, ups=4, cic=64, pro_act=LEAKY, t_lens=TL)),
+                   ("mfma flat", conv(Ci=256, cic=64, t_lens=TL)), ("glds", conv(Ci=256, flags=A_DMA, t_lens=TL)),
+                   ("mfma scalar epilogue", dict(g3, Co=30, ldy=30)), ("mfma mul 3", dict(g3, t_lens_mul=3)),
+                   ("mfma mul -1", dict(g3, t_lens_mul=-1)), ("mfma t_lens+2", dict(g3, t_lens=TL + 2)),
+                   ("frag32 snake", dict(f3, pro_act=SNAKE, pro_alpha=PTR["pro_alpha"])), ("frag32 ks 7", dict(f3, ks=7, pad=3)),
+                   ("frag32 ks 1 shortcut", conv(B=4, T=200, Ci=256, Co=256, cic=128, flags=FRAG32, t_lens=TL)),
+                   ("frag32 acc_in", dict(f3, acc_in=PTR["acc_in"], lda=256, bsa=200 * 256)),
+                   ("frag32 ups", conv(Ci=256, Co=128, ups=4, cic=128, flags=FRAG32, pro_act=LEAKY, t_lens=TL)),
+                   ("lane16", conv(Ci=256, ks=3, cic=128, flags=LANE16, pro_act=LEAKY, t_lens=TL)),
+                   ("narrow32", conv(Ci=128, Co=22, ks=7, cic=128, flags=NARROW32, outd=F32, pro_act=LEAKY, ldy=24, t_lens=TL)),
+                   ("x3", conv(Ci=64, ks=3, flags=X3, ind=F32, outd=F32, t_lens=TL)),
+                   ("f32", conv(Ci=64, ks=3, flags=WF32, ind=F32, outd=F32, t_lens=TL)),
+                   ("x3frag", conv(Ci=256, ks=3, cic=128, flags=FRAG32X3, ind=F32, outd=F32, pro_act=LEAKY, t_lens=TL)),
+                   ("rows", conv(B=1, T=20, Ci=512, Co=200, flags=ROWS, t_lens=TL))):
+        one(f"tlens.bad {lab}", d)
+
     # groups: the MRF trio, the DEEP split-K pair, their fallbacks (one after the other)
     def trio(Ci=128, B=1, T=100, r=True, flags=FRAG32, **kw):
         return [conv(B=B, T=T, Ci=Ci, Co=128, ks=k, cic=128, flags=flags, pro_act=SNAKE, res=r, **kw) for k in (3, 7, 11)]
@@ -385,6 +421,9 @@ def sweep_calls():
                ("pair.ticket", [conv(B=1, Ci=256, ks=3, cic=64, splitk=4, flags=SK_TICKET) for _ in range(2)]),
                ("pair.flat", [conv(B=1, Ci=256, cic=64, splitk=4) for _ in range(2)]),
                ("pair.frag32", trio()[:2]),
+               ("tlens.bad trio", trio(t_lens=PTR["t_lens"])),
+               ("tlens.bad pair", [conv(B=1, Ci=256, ks=3, cic=64, splitk=4, adain=True, t_lens=PTR["t_lens"]) for _ in range(2)]),
+               ("tlens pair.nosplit", [conv(B=1, Ci=256, ks=3, cic=64, t_lens=PTR["t_lens"]) for _ in range(2)]),
                ("pair.pro_part one", [conv(B=1, Ci=256, ks=3, cic=64, splitk=4, adain=True, **kw) for kw in
                                       ({}, dict(pro_part=PTR["pro_part"], pro_nch=2, pro_T=100, pro_ld=256))]),
                ("pair.pro_part both", [conv(B=1, Ci=256, ks=3, cic=64, splitk=4, adain=True, pro_part=PTR["pro_part"], pro_nch=2,
