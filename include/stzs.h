@@ -341,9 +341,17 @@ int stzs_attention(const stzs_attn_args* a, void* stream);
  * gx [B, T, ldg] f32 holds x W_ih^T + b_ih + b_hh for both directions (fwd 4H | rev 4H, gate
  * order i,f,g,o); whhT = W_hh^T as bf16 16x16x32 B fragments [2][4H/16][H/32][64][8]
  * (stzs/weights.py lstm_frags); H % 32 == 0, H <= 256; h written bf16 to y[b, t, dir*H + j].
- * Launches H/32 x ndir x ceil(B/64) co-resident workgroups that exchange h_t every step through
+ * Launches H/32 x ndir x groups co-resident workgroups, groups = ceil(B / rows): one group of up to 64
+ * utterances for B <= 16, else groups of 16 rows, or of 32 / 64 where 16 would give more than 63 groups x
+ * directions or more than 256 workgroups (csrc/lstm.hip lstm_group_rows; a shape that fits neither way is
+ * STZS_ESHAPE).  They exchange h_t every step through
  * `xchg` (write-through stores + agent-scope arrival counters in `sync`); spins are bounded and a
  * timeout ORs STZS_STATUS_LSTM_TIMEOUT into `*status` (and the last word of `sync`) instead of hanging.
+ * ndir = 1 runs the forward direction alone on the SAME operand layouts: whhT holds both directions'
+ * fragments (precise: hi of both directions, then lo of both -- the lo fragments are looked up behind two
+ * directions' hi ones whatever ndir is; the reverse direction's are not read) and gx keeps the forward gates
+ * in columns [0, 4H) of each row (ldg >= 4H; the two-direction buffer with ldg = 8H serves as it is).  Only
+ * y[b, t, 0 .. H) is written.
  * (DurationEncoder BiLSTMs, duration LSTM, shared LSTM) */
 typedef struct stzs_lstm_args {
     const float* gx;

@@ -650,3 +650,162 @@ def dur_logits(rows, nbins, seed=0):
 def dur_tie_width(nbins):
     """an fp32 serial sum of nbins sigmoids is within nbins * 2^-23 * nbins of the fp64 sum"""
     return nbins * 2.0 ** -23 * nbins
+
+
+# ---- LSTM recurrence: the teacher-forced fp64 reference (tests/test_gpu_lstm_parity.py, test_refops_lstm.py) ----
+# A free-running bf16 recurrence amplifies every rounding flip of h over the remaining steps, so a per-element bound on
+# it is useless.  Teacher forcing removes the amplification: at every step the reference takes as h_{t-1} the values the
+# kernel itself stored in y at the previous position of that direction (zeros at the first step) -- in bf16 mode
+# bit for bit what the workgroups exchanged -- and carries only the cell state c, in fp64, with a running error bound.
+
+U32 = 2.0 ** -24  # the unit roundoff of fp32
+
+
+def split_hi_lo(y):
+    """fp32 -> (hi, lo) fp64 as the precise kernel splits the h it exchanges: hi = bf16(y) to nearest even, lo =
+    bf16(y - hi) (the difference is exact in fp32)"""
+    y = y.float()
+    hi = y.to(torch.bfloat16).float()
+    return hi.double(), (y - hi).to(torch.bfloat16).double()
+
+
+def half_ulp_bf16(h):
+    """half the spacing of bf16 at round_bf16(h) (exact, not 2^-8 |h|, which is up to twice as loose); 0 at h == 0"""
+    r = round_bf16(torch.where(h == 0, torch.ones_like(h), h)).double()
+    _, e = torch.frexp(r)  # |r| = m 2^e, m in [0.5, 1): the spacing above |r| is 2^(e - 8)
+    return torch.where(h == 0, torch.zeros_like(h), torch.ldexp(torch.ones_like(h), e.clamp_min(-125) - 9))
+
+
+def _sig_err(pre, e_pre):
+    # sigmoid = rcp(1 + exp(-x)), exp(x) = v_exp_f32(x log2 e): the argument product's rounding |x| u relative, v_exp
+    # and v_rcp 1 ulp each, the add 1/2 ulp; doubled as dense_ratio doubles its total; sigmoid' <= 1/4, sigmoid <= 1
+    return e_pre / 4 + (pre.abs() + 3) * 2 * U32
+
+
+def _tanh_err(pre, e_pre=0.0):
+    # tanh = 1 - 2 rcp(1 + exp(2x)) with one fma: twice the argument, 1 + 1 + 1/2 + 1/2 ulp, doubled; tanh' <= 1
+    return e_pre + (2 * pre.abs() + 3) * 4 * U32
+
+
+def lstm_tf_ref(gx, w_hh, y, H, ndir, lens=None, precise=False):
+    """The teacher-forced reference of stzs_lstm.  gx [B, T, ndir 4H] fp32 (gate order i, f, g, o per direction: the C
+    ABI's layout), w_hh a list of ndir [4H, H] tensors as the kernel holds them (bf16 mode: the bf16-rounded values;
+    precise: the (hi, lo) pair of stzs.weights.split_bf16), y [B, T, ndir H] what the kernel stored (bf16 | fp32), lens
+    [B] | None -> (h_ref, E_h) fp64 [B, T, ndir H]: the output given the kernel's own h_{t-1}, and the bound of what an
+    fp32 evaluation may differ from it by.
+
+    Per step and gate, bf16 mode: pre = gx + h_prev W^T, terms = |gx| + |h_prev| |W|^T, e_pre = 2 (H + 4) 2^-24 terms
+    (dense_ratio's constants).  Precise: h_prev = hi + lo as split_hi_lo, pre = gx + h_lo W_hi + h_hi W_lo + h_hi W_hi
+    (the kernel's three products; lo lo is absent on purpose), terms the same on absolute values, e_pre = 2 (3H + 4)
+    2^-24 terms.  Gate errors (u = 2^-24): sigmoid e = e_pre / 4 + (|pre| + 3) 2u, tanh e = e_pre + (2 |pre| + 3) 4u
+    (_sig_err / _tanh_err: hardware v_exp_f32 and v_rcp_f32 at 1 ulp each).  The same forms serve the precise mode's
+    libm expf / tanhf, which rests on the device library being within about 5 fp32 ulps there -- unconfirmed: its
+    accuracy table was not at hand when this was written.
+    Cell: c = f c + i g,
+    E_c <- f E_c + |c_prev| e_f + e_f E_c + |g| e_i + i e_g + e_i e_g + 2u (|f c_prev| + |i g|);
+    output: h = o tanh(c), E_h = |tanh c| e_o + (o + e_o) (E_c + A_tanh(c)) + u |h|, A_tanh = _tanh_err(c).
+    Ragged rows: where t >= clamp(lens[b], 1, T), c, E_c, h and E_h are 0, as the kernel sets them after its update."""
+    B, T = gx.shape[:2]
+    assert gx.shape[2] == ndir * 4 * H and y.shape == (B, T, ndir * H) and len(w_hh) == ndir
+    gx, yd = gx.double(), y.double()
+    K = 3 * H if precise else H
+    ln = None if lens is None else torch.as_tensor(lens).long().clamp(1, T)
+    h_ref, E_h = torch.zeros(B, T, ndir * H, dtype=torch.float64), torch.zeros(B, T, ndir * H, dtype=torch.float64)
+    for d in range(ndir):
+        if precise:
+            whi, wlo = (w.double().t() for w in w_hh[d])
+        else:
+            w = w_hh[d].double().t()
+        c = torch.zeros(B, H, dtype=torch.float64)
+        Ec = torch.zeros(B, H, dtype=torch.float64)
+        for s in range(T):
+            t = s if d == 0 else T - 1 - s
+            tp = t - 1 if d == 0 else t + 1
+            g_t = gx[:, t, d * 4 * H:(d + 1) * 4 * H]
+            hp = yd[:, tp, d * H:(d + 1) * H] if s else torch.zeros(B, H, dtype=torch.float64)
+            if precise:
+                hi, lo = split_hi_lo(y[:, tp, d * H:(d + 1) * H]) if s else (hp, hp)
+                pre = g_t + lo @ whi + hi @ wlo + hi @ whi
+                terms = g_t.abs() + lo.abs() @ whi.abs() + hi.abs() @ wlo.abs() + hi.abs() @ whi.abs()
+            else:
+                pre = g_t + hp @ w
+                terms = g_t.abs() + hp.abs() @ w.abs()
+            e_pre = 2.0 * (K + 4) * U32 * terms
+            pi, pf, pg, po = pre.split(H, 1)
+            ei, ef, eg, eo = (_sig_err(p, e) if k != 2 else _tanh_err(p, e)
+                              for k, (p, e) in enumerate(zip((pi, pf, pg, po), e_pre.split(H, 1))))
+            ig, fg, gg, og = torch.sigmoid(pi), torch.sigmoid(pf), torch.tanh(pg), torch.sigmoid(po)
+            Ec = (fg * Ec + c.abs() * ef + ef * Ec + gg.abs() * ei + ig * eg + ei * eg
+                  + 2 * U32 * ((fg * c).abs() + (ig * gg).abs()))
+            c = fg * c + ig * gg
+            th = torch.tanh(c)
+            h = og * th
+            Eh = th.abs() * eo + (og + eo) * (Ec + _tanh_err(c)) + U32 * h.abs()
+            if ln is not None:
+                keep = (t < ln)[:, None].double()
+                c, Ec, h, Eh = c * keep, Ec * keep, h * keep, Eh * keep
+            h_ref[:, t, d * H:(d + 1) * H], E_h[:, t, d * H:(d + 1) * H] = h, Eh
+    return h_ref, E_h
+
+
+def lstm_tf_check(y, h_ref, E_h, bf16_out):
+    """y against lstm_tf_ref's (h_ref, E_h) -> (ratio, flip_share).  ratio = max |y - h_ref| / bound with bound =
+    half_ulp_bf16(h_ref) + E_h (1 + 2^-8) for a bf16 output (the rounding of a value within E_h of h_ref) and bound = E_h
+    for an fp32 one; where the bound is 0 (a ragged row's tail) anything but an exact 0 gives inf.  flip_share (bf16
+    output; 0.0 otherwise): the share of the non-zero reference elements whose bits differ from round_bf16(h_ref).
+    The first must be <= 1, the second <= 0.01 (staged_check's cap)."""
+    d = (y.double() - h_ref).abs()
+    bound = half_ulp_bf16(h_ref) + E_h * (1 + 2.0 ** -8) if bf16_out else E_h
+    ratio = torch.where(bound > 0, d / bound.clamp_min(1e-300), torch.where(d == 0, 0.0, float("inf")).double())
+    share = 0.0
+    if bf16_out:
+        nz = h_ref != 0
+        want = round_bf16(torch.where(nz, h_ref, torch.ones_like(h_ref)))
+        diff = (_bits(y.to(torch.bfloat16)) != _bits(want)) & nz
+        share = diff.sum().item() / max(int(nz.sum().item()), 1)
+    return ratio.max().item(), share
+
+
+def lstm_emulate(gx, w_hh, H, ndir, lens=None, mutate=None, precise=False):
+    """An fp32 model of the kernel on the CPU: h exchanged as bf16 (precise: as the hi | lo pair, y fp32), c in fp32,
+    torch's sigmoid / tanh.  Arguments as lstm_tf_ref -> y [B, T, ndir H] bf16 (precise: fp32).  mutate: one mistake
+    for tests/test_refops_lstm.py -- "w" one W_hh element off by 0.05, "swap_if" the i and f blocks of the recurrent
+    product swapped, "stale" h_{t-2} used from step 2 on, "zero_row" the longest row's exchanged h zeroed at one step per
+    direction with its y correct, "c_drift" c scaled by 1 + 1e-4 every step."""
+    B, T = gx.shape[:2]
+    ln = None if lens is None else torch.as_tensor(lens).long().clamp(1, T)
+    y = torch.zeros(B, T, ndir * H, dtype=torch.float32 if precise else torch.bfloat16)
+    zrow = 0 if ln is None else int(ln.argmax())  # "zero_row": the longest row
+    zlen = T if ln is None else int(ln[zrow])
+    for d in range(ndir):
+        ws =[w.float().clone() for w in w_hh[d]] if precise else [w_hh[d].float().clone()]
+        if mutate == "w":
+            ws[0][2 * H + 5, 3] += 0.05
+        c = torch.zeros(B, H)
+        sent = [torch.zeros(B, H)]  # what was exchanged, per step (fp32 values of the bf16 | hi + lo)
+        for s in range(T):
+            t = s if d == 0 else T - 1 - s
+            hp = sent[-2] if mutate == "stale" and s >= 2 else sent[-1]
+            if precise:
+                hi = hp.to(torch.bfloat16).float()
+                lo = (hp - hi).to(torch.bfloat16).float()
+                rec = lo @ ws[0].t() + hi @ ws[1].t() + hi @ ws[0].t()
+            else:
+                rec = hp @ ws[0].t()
+            if mutate == "swap_if":
+                rec = torch.cat([rec[:, H:2 * H], rec[:, :H], rec[:, 2 * H:]], 1)
+            pi, pf, pg, po = (gx[:, t, d * 4 * H:(d + 1) * 4 * H].float() + rec).split(H, 1)
+            c = torch.sigmoid(pf) * c + torch.sigmoid(pi) * torch.tanh(pg)
+            if mutate == "c_drift":
+                c = c * (1 + 1e-4)
+            h = torch.sigmoid(po) * torch.tanh(c)
+            if ln is not None:
+                keep = (t < ln)[:, None]
+                c, h = c * keep, h * keep
+            h = h if precise else h.to(torch.bfloat16)
+            y[:, t, d * H:(d + 1) * H] = h
+            x = h.float().clone()
+            if mutate == "zero_row" and t == (0 if d == 0 else zlen - 1):  # (a step whose h the next one reads)
+                x[zrow] = 0
+            sent.append(x)
+    return y

@@ -546,8 +546,9 @@ def _v0_lstm(In=640, H=256, seed=9):
 
 @pytest.mark.parametrize("B,T", [(64, 80), (40, 23), (1, 80), (2, 50), (65, 7)])
 def test_lstm_v0_width(eng, B, T):
-    """the benchmarked LSTM shape: H = 256 (8 exchanging workgroups per direction), 16-64 utterances per
-    group (1-4 MFMA row tiles, multi-row exchange loads) vs torch.nn.LSTM on identical bf16 inputs; B = 1 / 2 and
+    """the benchmarked LSTM shape: H = 256 (8 exchanging workgroups per direction) vs torch.nn.LSTM on identical bf16
+    inputs.  Every group here is ONE MFMA row tile: B = 64 is four 16-row groups, B = 40 groups of 16, 16 and 8 rows,
+    B = 65 four 16-row groups and a 1-row one (taller groups: tests/test_gpu_lstm_parity.py); B = 1 / 2 and
     the 1-row last group of B = 65 hand h over as tagged granules (csrc/lstm.hip TAG_ROWS), run twice: the second
     call must not see the first call's tags (bit-identical).
     tolerance: max-abs error <= 2e-2 of max|ref| (bf16 h exchanged every step, fp32 cell state)."""
