@@ -36,7 +36,12 @@ enum { STZS_F32 = 0, STZS_BF16 = 1, STZS_I32 = 2, STZS_F8 = 3 /* OCP e4m3fn (gfx
 enum { STZS_ACT_NONE = 0, STZS_ACT_LEAKY = 1, STZS_ACT_SNAKE = 2, STZS_ACT_GELU = 3, STZS_ACT_SILU = 4 };
 enum { STZS_PRO_NONE = 0, STZS_PRO_ADAIN = 1 };
 /* stzs_conv_args.flags: the caller guarantees that for a ks=1 bf16 linear every input row can be
- * read over [0, ci_pad) channels (row padding inside the buffer) -> A streams by LDS-DMA */
+ * read over [0, ci_pad) channels (row padding inside the buffer) -> A streams by LDS-DMA.
+ * What the kernel touches (tests/test_gpu_linear_probe.py reads it out exactly): x over [0, ci_pad) of every row
+ * < B * T_in -- the channels [Ci, ci_pad) meet zero weights and must be FINITE, not zero -- and nothing else of x (a
+ * tile's rows past B * T_in re-read the last row); of y only [0, Co) of the rows < B * T_out, also where Co % 8 != 0
+ * or ldy % 8 != 0 (the scalar epilogue); x_scale (fp8) at rows < B * T_in only; with split-K every counter is left
+ * zero and nothing past stzs_conv_splitk_workspace bytes of splitk_ws is written. */
 #define STZS_CONV_A_DMA 8
 
 /* ---- library ---- */
@@ -189,7 +194,11 @@ size_t stzs_conv_splitk_workspace(int64_t rows, int32_t co_pad, int32_t splitk);
  * splitk_ctr (one zeroed uint32 per tile, left zeroed).  Epilogue:
  * bias, epi_act NONE | GELU | SILU, FLAT gate, residual, alpha, beta * acc_in.  The per-element summation order depends on
  * K and Z only (batch-invariant).  Replaces gemm_glds for 100-row linears whose 8-32 tiles would stream all of K
- * through 8-32 CUs (SURVEY §8(a) a2 at B = 1). */
+ * through 8-32 CUs (SURVEY §8(a) a2 at B = 1).
+ * Memory (tests/test_gpu_linear_probe.py): x is read over [0, ci_pad) of every row < B * T_in and must be finite there
+ * (ldx >= ci_pad; a row block's rows past B * T_in re-read the last row); nothing outside [0, Co) x rows < B * T_in of
+ * y is written, the waves of a partial 16-column tile included; nothing past stzs_conv_rows_workspace bytes of
+ * splitk_ws. */
 #define STZS_CONV_ROWS 2048
 /* flags bit (with STZS_CONV_W_FRAG32 and ups > 0, refl in {0, 1}, Co % 128 == 0): the polyphase ConvTranspose with
  * the generator's 1x1 noise conv fused as ONE extra K-step per 128-column tile (stzs/weights.py pack_ups_noise):
@@ -303,7 +312,12 @@ int stzs_row_layernorm(const stzs_rowln_args* a, void* stream);
  * by pro_cscale and rounded to bf16; ci_pad / 32 in {4, 8, 16, 32, 64}; x 16-B aligned, ldx / bsx multiples of 8;
  * epilogue adds the FLAT gate and the residual).  splitk = Z in {2, 4} with ci_pad / 32 / Z in {4, 8, 16}: K slices
  * handed to each tile's last arriver through splitk_ws (stzs_conv_rows_workspace(rows, Co, Z) bytes suffice) and
- * splitk_ctr (zeroed uint32 tickets, left zero), summed in slice order. */
+ * splitk_ctr (zeroed uint32 tickets, left zero), summed in slice order.
+ * Memory (tests/test_gpu_linear_probe.py): ln = NULL reads x over [0, ci_pad) of every row < B * T_in (finite there);
+ * with ln the rows ln->x[r * ldx + [0, C)], r < R, and G / Bt at group r / gdiv only; either way nothing outside
+ * [0, Co) x rows < B * T_in of y is written (waves past Co of a sliced tile still meet the barriers and store
+ * nothing).  The fused operand image is the fp64 LayerNorm of the stored rows to within one bf16 ulp (or 2^-8 |ref| +
+ * 64 2^-24 of the magnitudes where the result cancels). */
 int stzs_ln_linear(const stzs_conv_args* a, const stzs_rowln_args* ln, void* stream);
 
 /* per-row fp8 quantisation with a power-of-two row scale (exact scaling, as MX block scales):

@@ -162,7 +162,7 @@ def same_bits(a, b):
     """bit-for-bit equality (distinguishes -0 from +0, equates identical NaNs)"""
     if a.dtype != b.dtype or a.shape != b.shape:
         return False
-    vt = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    vt = {1: torch.int8, 2: torch.int16, 4: torch.int32}[a.element_size()]
     return torch.equal(a.contiguous().view(vt), b.contiguous().view(vt))
 
 
@@ -213,12 +213,14 @@ def staged_check(got, s, sbf, mag):
 
 
 def conv_terms_ref(xhat, w, b, *, pad=0, dil=1, stride=1, res=None, res_tdiv=1, out_scale=1.0, acc_in=None, beta=0.0,
-                   ups=0, ups_pad=0, refl=0):
+                   ups=0, ups_pad=0, refl=0, gate=None):
     """conv_ref / convT_ref on already-staged operands, in fp64, with the magnitude its rounding errors scale with.
     xhat [B, T, Ci] (the staged values), w [Co, Ci, k] (ups > 0: ConvTranspose1d weights [Ci, Co, 2 ups], stride ups,
     padding ups_pad, ReflectionPad(refl, 0)) as the kernel holds them (bf16-rounded by the caller), b [Co] | None ->
-    (y, terms) [B, T_out, Co] fp64; terms is the same conv on |xhat|, |w|, |b|, plus |res| and |beta acc_in|."""
-    def run(x, ww, bb, r, a):
+    (y, terms) [B, T_out, Co] fp64; terms is the same conv on |xhat|, |w|, |b|, plus |res| and |beta acc_in|.
+    gate [B, Co] | None: the per-utterance DiT gate of the linears, on conv + bias and before the residual
+    (include/stzs.h: y = ((W x + b) gate[utterance] + res) alpha + beta acc_in); terms takes |gate|."""
+    def run(x, ww, bb, r, a, gt):
         x = x.double().transpose(1, 2)
         bb = bb.double() if bb is not None else None
         if ups:
@@ -228,6 +230,8 @@ def conv_terms_ref(xhat, w, b, *, pad=0, dil=1, stride=1, res=None, res_tdiv=1, 
         else:
             y = F.conv1d(x, ww.double(), bb, stride=stride, padding=pad, dilation=dil)
         y = y.transpose(1, 2)
+        if gt is not None:
+            y = y * gt.double()[:, None, :]
         if r is not None:
             r = r.double()
             if res_tdiv > 1:
@@ -238,9 +242,9 @@ def conv_terms_ref(xhat, w, b, *, pad=0, dil=1, stride=1, res=None, res_tdiv=1, 
             y = y + beta * a.double()
         return y
     ab = lambda t: t.abs() if t is not None else None
-    y = run(xhat, w, b, res, acc_in)
+    y = run(xhat, w, b, res, acc_in, gate)
     out_scale, beta = abs(out_scale), abs(beta)
-    return y, run(xhat.abs(), w.abs(), ab(b), ab(res), ab(acc_in))
+    return y, run(xhat.abs(), w.abs(), ab(b), ab(res), ab(acc_in), ab(gate))
 
 
 def dense_ratio(got, ref, terms, K, bf16_out):
@@ -272,7 +276,7 @@ def delta_weights_T(Ci, Co, k, j0, m=0):
 def fill_bits(shape, dtype, fill, device="cpu"):
     """a tensor of `dtype` filled with `fill`: a float value, or an int bit pattern (e.g. a NaN payload)"""
     if isinstance(fill, int):
-        it = {2: torch.int16, 4: torch.int32}[torch.empty(0, dtype=dtype).element_size()]
+        it = {1: torch.int8, 2: torch.int16, 4: torch.int32}[torch.empty(0, dtype=dtype).element_size()]
         bits = fill - (1 << (8 * it.itemsize)) if fill >= 1 << (8 * it.itemsize - 1) else fill
         return torch.full(shape, bits, dtype=it, device=device).view(dtype)
     return torch.full(shape, fill, dtype=dtype, device=device)
@@ -300,7 +304,7 @@ def guards_intact(buf, view, fill, C=None):
 
 
 def _bits(t):
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
+    return t.contiguous().view({1: torch.int8, 2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _first(mask):
@@ -809,3 +813,302 @@ def lstm_emulate(gx, w_hh, H, ndir, lens=None, mutate=None, precise=False):
                 x[zrow] = 0
             sent.append(x)
     return y
+
+
+# ---- the linears: exact operand probes and per-element bounds (tests/test_gpu_linear_probe.py, test_refops_linear.py,
+# the --linear-cases mode of tools/dispatch_trace.py) ----
+# A linear is a conv with one tap: with delta_weights(Co, Ci, 1, 0, m), bias 0 and no epilogue operands the output IS
+# the kernel's staged A operand, through split-K, the wave-partial sums and the fp8 dequantisation (every partial is
+# 0 + x).
+
+from collections import namedtuple
+
+LIN_DT = {"bf16": torch.bfloat16, "f32": torch.float32, "f8": torch.float8_e4m3fn}
+LIN_POISON = 2.0 ** 100   # finite: 0 * poison = 0
+LIN_POISON_F8 = 0x7E      # e4m3fn 448, the largest finite code
+LIN_SENT = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FC0A5A5}  # NaN payloads: a write of any value shows
+LIN_ROWS = ((1, 1), (3, 5), (1, 64), (5, 13), (2, 50), (3, 43))  # (B, T): 1, 15, 64, 65, 100, 129 rows
+
+# kern: glds (gemm_glds, 64-row tiles) | glds128 (its 128-row tile) | f8 (gemm_glds fp8) | rows (gemm_rows) | rows16;
+# Z: K slices (0: unsplit); idt / odt: keys of LIN_DT; ypads: guarded()'s pads of y; ids: STZS_CONV_LINEAR_IDS;
+# cscale: the fp32 input's scale
+LinCase = namedtuple("LinCase", "kern B T Ci Co Z idt odt ypads ids cscale", defaults=("bf16", "bf16", (2, 8, 8), 0, 1.0))
+
+
+def lin_id(c):
+    return (f"{c.kern}-{c.B}x{c.T}-{c.Ci}to{c.Co}-Z{c.Z}-{c.idt}-{c.odt}" + ("-ldy24" if c.ypads[1:] == (0, 0) else "") +
+            ("-ids" if c.ids else "") + (f"-cs{c.cscale}" if c.cscale != 1.0 else ""))
+
+
+def lin_ci_pad(c):
+    """stzs.weights.pack_conv's / pack_conv_f8's K padding, restated"""
+    if c.kern == "f8":
+        return (c.Ci + 63) // 64 * 64
+    cic = 32 if c.Ci <= 32 else (64 if c.Ci <= 64 else 128)
+    return (c.Ci + cic - 1) // cic * cic
+
+
+def gemm_tile_rows(M, co_pad, ncu):
+    """csrc/gemm.hip gemm_launch's tile height, restated: 128-row tiles run two workgroups per CU, 64-row tiles three,
+    and a 64-row tile costs 0.6 of a 128-row one -- 64 where 6 r64 < 10 r128 (r: rounds of resident workgroups)"""
+    gy = co_pad // 128
+    n128, n64 = (M + 127) // 128 * gy, (M + 63) // 64 * gy
+    r128, r64 = (n128 + 2 * ncu - 1) // (2 * ncu), (n64 + 3 * ncu - 1) // (3 * ncu)
+    return 64 if 6 * r64 < 10 * r128 else 128
+
+
+def gemm_tile128_rows(ncu, Co=2048, T=50, limit=12800):
+    """the row count of the 128-row-tile probe: 64 x 50 rows where the rule gives them the 128-row tile (256 CUs),
+    else the smallest multiple of T up to `limit` that it does; None if there is none"""
+    for M in [64 * T] + list(range(T, limit + 1, T)):
+        if gemm_tile_rows(M, (Co + 127) // 128 * 128, ncu) == 128:
+            return M
+    return None
+
+
+def linear_cases(ncu=256):
+    """the identity-probe table of tests/test_gpu_linear_probe.py (section A): axis sweeps over the K-step counts, the
+    row counts, the output widths and the dtypes of every kernel form, not their product"""
+    C, out = LinCase, []
+    big = (3, 43)
+    # gemm_glds, 64-row tiles: K-steps 1, 2, 4, 12, 16; Ci < ci_pad (22, 80); rows; widths; the scalar epilogue
+    out += [C("glds", *big, Ci, 200, 0, "bf16", o) for Ci in (22, 64, 80, 384, 512) for o in ("bf16", "f32")]
+    out += [C("glds", B, T, 80, 80, 0) for B, T in LIN_ROWS if (B, T) != big]
+    out += [C("glds", 5, 13, 128, Co, 0, "bf16", "f32") for Co in (8, 80, 128, 384)] + [C("glds", 5, 13, 128, 8, 0)]
+    out += [C("glds", *big, 64, 22, 0, "bf16", o, (2, 0, 0)) for o in ("bf16", "f32")]
+    M = gemm_tile128_rows(ncu)
+    if M is not None:
+        out += [C("glds128", M // 50, 50, 32, 2048, 0, "bf16", o) for o in ("bf16", "f32")]
+        if gemm_tile_rows(3137, 2048, ncu) == 128:
+            out += [C("glds128", 1, 3137, 32, 2048, 0)]
+        if gemm_tile_rows(3073, 2048, ncu) == 128:
+            out += [C("glds128", 7, 439, 32, 2048, 0)]  # (one row in the last 128-row tile)
+    # split-K: slices of 1, 2, 3 and 6 K-steps
+    for Ci, Z in ((64, 2), (128, 2), (128, 4), (384, 4), (384, 2)):
+        out += [C("glds", *big, Ci, 200, Z, "bf16", o, ids=i) for o in ("bf16", "f32") for i in (0, 1)]
+    out += [C("glds", B, T, 128, 80, 4, "bf16", "f32") for B, T in ((1, 1), (5, 13))]
+    out += [C("glds", *big, 128, 22, 2, "bf16", "f32", (2, 0, 0))]
+    # fp8: K-steps 1, 2, 3, 5
+    out += [C("f8", *big, Ci, 200, 0, "f8", o) for Ci in (64, 128, 192, 320) for o in ("f32", "bf16")]
+    out += [C("f8", B, T, 128, 80, 0, "f8", "f32") for B, T in LIN_ROWS[:4]]
+    out += [C("f8", *big, 64, 22, 0, "f8", "f32", (2, 0, 0))]
+    # gemm_rows: Z x K-steps per wave 1, 2, 4, 16; rows across the 64 / 128-row block switch; widths; dtypes
+    for kern, KZ in (("rows", ((128, 0), (256, 0), (256, 2), (512, 0), (512, 2), (512, 4), (2048, 0))),
+                     ("rows16", ((128, 0), (256, 0), (512, 0), (1024, 0), (2048, 0), (256, 2), (1024, 2), (512, 4),
+                                 (2048, 4)))):
+        out += [C(kern, *big, Ci, 200, Z, "bf16", "f32") for Ci, Z in KZ]
+        out += [C(kern, *big, 256, 80, Z, "bf16", "bf16") for Z in (0, 2)]
+        out += [C(kern, B, T, 256, 80, 2) for B, T in LIN_ROWS if (B, T) != big]
+        out += [C(kern, B, T, 128, 80, 0, "bf16", "f32") for B, T in LIN_ROWS if (B, T) != big]
+        out += [C(kern, 5, 13, 128, Co, 0, "bf16", "f32") for Co in (16, 22, 200)]
+        out += [C(kern, 5, 13, 256, 22, 2, "bf16", "f32", (2, 0, 0))]
+        out += [C(kern, 5, 13, 256, 80, Z, "f32", "f32", cscale=0.5) for Z in (0, 2)]
+    return out
+
+
+def lin_expected_launch(c):
+    """what the case must launch: (a substring of the kernel's name, grid x, y, z) -- the launchers' geometry restated
+    (csrc/gemm.hip, rows.hip, lnrows.hip; rows16 unsplit up to 16 K-steps: one 16-column tile per workgroup, the
+    default of STZS_ROWS16_WPG)"""
+    M, Z = c.B * c.T, max(c.Z, 1)
+    if c.kern in ("glds", "glds128", "f8"):
+        bt = 128 if c.kern == "glds128" else 64
+        return "gemm_glds", (M + bt - 1) // bt, (c.Co + 127) // 128, Z
+    if c.kern == "rows":
+        blk = 64 if M <= 64 else 128
+        return "gemm_rows", (c.Co + 15) // 16, (M + blk - 1) // blk, Z
+    wide = Z > 1 or lin_ci_pad(c) // 32 > 16  # (four 16-column tiles per workgroup: the sliced form, and 32 / 64 K-steps)
+    return "rows16", (c.Co + 63) // 64 if wide else (c.Co + 15) // 16, (M + 15) // 16, Z
+
+
+def linear_probe_expect(xs, Co, m=0):
+    """the exact output of delta_weights(Co, Ci, 1, 0, m) on the staged operand xs [B, T, Ci]: column co holds
+    xs[:, :, co + m Co] where that exists, +0 elsewhere -> [B, T, Co] in xs's dtype"""
+    B, T, Ci = xs.shape
+    E = torch.zeros(B, T, Co, dtype=xs.dtype, device=xs.device)
+    n = max(0, min(Co, Ci - m * Co))
+    E[:, :, :n] = xs[:, :, m * Co:m * Co + n]
+    return E
+
+
+def first_diff(got, want):
+    """None where got and want agree in bits, else a message naming the first (utterance, row, column)"""
+    bad = _bits(got) != _bits(want)
+    if not bool(bad.any()):
+        return None
+    i = _first(bad)
+    return (f"{int(bad.sum())} elements differ; first at (utterance, row, column) {i}: got {float(got[i])!r}, "
+            f"expected {float(want[i])!r}")
+
+
+def e4m3_case(B, T, Ci, seed=0):
+    """-> (codes uint8 [B, T, Ci], x_scale fp32 [B T]): random finite e4m3fn codes with, in every row that has room,
+    both zeros, the smallest and largest subnormals of both signs and +-448; the row scales are powers of two,
+    distinct per row (2^(r - R / 2): their products with 448^2 stay normal fp32 / bf16 numbers)"""
+    g = torch.Generator().manual_seed(1000 + seed + B * T + Ci)
+    codes = torch.randint(0, 256, (B, T, Ci), generator=g, dtype=torch.int32)
+    codes = torch.where(codes & 0x7F == 0x7F, codes - 1, codes).to(torch.uint8)  # (0x7F / 0xFF: NaN)
+    special = torch.tensor([0x00, 0x80, 0x01, 0x81, 0x07, 0x87, 0x7E, 0xFE], dtype=torch.uint8)
+    for r in range(B * T):
+        o = (r * 5) % (Ci - 8 + 1)
+        codes.view(B * T, Ci)[r, o:o + 8] = special
+    R = B * T
+    return codes, torch.ldexp(torch.ones(R), torch.arange(R) - R // 2)
+
+
+def e4m3_value(codes):
+    """uint8 codes -> their fp32 values"""
+    return codes.view(torch.float8_e4m3fn).float()
+
+
+def quant_rows_ref(x):
+    """stzs_quant_rows restated (include/stzs.h): the power-of-two row scale 2^k, the smallest with amax / 2^k <= 448,
+    then RNE e4m3fn codes of x / 2^k -> (codes uint8, scale fp32 [rows])"""
+    amax = x.abs().amax(-1)
+    m, e = torch.frexp(amax)
+    k = torch.where(m <= 0.875, e - 9, e - 8)
+    k = torch.where(amax > 0, k, torch.zeros_like(k))
+    scale = torch.ldexp(torch.ones_like(amax), k)
+    return (x / scale[..., None]).to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def act_ratio(got, z, terms, K, act, bf16_out):
+    """GELU / SiLU epilogue against the fp64 pre-activation z and its terms: the largest |got - act(z)| / bound, bound =
+    1.13 (the Lipschitz bound of both) x dense_ratio's accumulation bound + 4e-7 (1 + |z|) (fast_erf 1.5e-7, __expf)
+    (+ 2^-8 |ref| for a bf16 output): tests/test_gpu_conv_probe.py test_dense_flat_gemm_act's bound"""
+    ref = 0.5 * z * (1 + torch.erf(z / math.sqrt(2))) if act == "gelu" else z / (1 + torch.exp(-z))
+    bound = 1.13 * 2 * (K + 4) * 2.0 ** -24 * terms + 4e-7 * (1 + z.abs())
+    if bf16_out:
+        bound = bound + ref.abs() * 2.0 ** -8
+    return ((got.double() - ref).abs() / bound).max().item()
+
+
+def layernorm_ref64(x, G, Bt, grp, gadd, eps=1e-5):
+    """the modulated row LayerNorm in fp64 on the stored rows x [R, C]: (x - mu) rstd (gadd + G[grp]) + Bt[grp]
+    -> (ref, terms = (|x| + |mu|) rstd |g| + |Bt|: what its fp32 evaluation errors scale with)"""
+    xx = x.double()
+    mu, rs = xx.mean(1, keepdim=True), 1 / torch.sqrt(xx.var(1, unbiased=False, keepdim=True) + eps)
+    gg = gadd + (G.double()[grp] if G is not None else 0.0)
+    bt = Bt.double()[grp] if Bt is not None else torch.zeros_like(xx)
+    return (xx - mu) * rs * gg + bt, (xx.abs() + mu.abs()) * rs * abs(gg) + bt.abs()
+
+
+def layernorm_image_ok(img, ref, terms):
+    """tests/test_gpu_norm_edges.py test_row_layernorm_edges' rule for a bf16 image: every element within one bf16 ulp of
+    the rounded reference, or within 2^-8 |ref| + 64 2^-24 terms -> (all ok?, largest ulp distance, elements past one)"""
+    u = ulp_dist(img, ref.float().to(torch.bfloat16))
+    err = (img.double() - ref).abs()
+    ok = (u <= 1) | (err <= 2.0 ** -8 * ref.abs() + 64 * 2.0 ** -24 * terms)
+    return bool(ok.all()), int(u.max()), int((u > 1).sum())
+
+
+def lin_x_pads(c, poisoned):
+    """guarded()'s pads of a case's x: the columns behind the row reach c0 + ci_pad <= ld (the engine routes a linear
+    whose rows are not readable over ci_pad channels away from the GEMMs); fp8 rows are 16-byte aligned"""
+    extra = lin_ci_pad(c) - (c.Ci + 7) // 8 * 8
+    al = 16 if c.kern == "f8" else 8
+    return (3, al, al + extra) if poisoned else (0, 0, extra)
+
+
+def lin_launch(eng, c, cw, xa, ya, *, x_scale=None, **epi):
+    """one linear through the engine's routing: eng.conv(..., collect=[]) fills and routes the stzs_conv_args, the form
+    the case names is asserted (flags, splitk, the entry point _conv_entry returns), then the library call is made here.
+    (rows16: the engine does not collect a stzs_ln_linear call, so conv() launches it itself, after the same
+    assertions.)  -> the args"""
+    from stzs import _lib as L
+    label, small = lin_id(c), c.kern in ("rows", "rows16")
+    rec, entry = [], eng._conv_entry
+
+    def checked(a, *rest, **kw):
+        fn, args, fused = entry(a, *rest, **kw)
+        if small:
+            assert a.flags & L.CONV_ROWS and not a.flags & 8, (label, a.flags)
+        else:
+            assert a.flags & 8 and not a.flags & L.CONV_ROWS, (label, a.flags)
+        want = eng.lib.stzs_ln_linear if c.kern == "rows16" else eng.lib.stzs_conv1d
+        assert fn is want and not fused, (label, "entry point")
+        assert a.splitk == c.Z if c.Z > 1 else a.splitk <= 1, (label, a.splitk)
+        rec.append((a, fn, args))
+        return fn, args, fused
+
+    keep = eng.rows16, eng.rows16_maxk
+    eng._conv_entry = checked
+    eng.rows16, eng.rows16_maxk = c.kern == "rows16", max(eng.rows16_maxk, 2048 if c.kern == "rows16" else 0)
+    try:
+        eng.conv(cw, xa, ya, collect=None if c.kern == "rows16" else [], rows=max(c.Z, 1) if small else 0,
+                 splitk=0 if small else c.Z, cscale=c.cscale, x_scale=x_scale,
+                 flags=L.CONV_LINEAR_IDS if c.ids else 0, what=label, **epi)
+    finally:
+        eng._conv_entry = entry
+        eng.rows16, eng.rows16_maxk = keep
+    a, fn, args = rec[0]
+    if c.kern != "rows16":
+        rc = fn(*args, eng.stream())
+        assert rc == 0, f"{label}: the library call returned {rc}"
+    return a
+
+
+LIN_PACKED = {}  # packed one-hot weights, by (device, fp8?, Co, Ci, block)
+
+
+def lin_pack(c, w, b=None, key=None, dev="cpu"):
+    """pack (and cache, under `key`) the Linear weight w [Co, Ci] for the case's kernel on `dev`"""
+    if key is not None and (dev, key) in LIN_PACKED:
+        return LIN_PACKED[dev, key]
+    from stzs.weights import Arena, pack_conv, pack_conv_f8
+    A = Arena()
+    cw = pack_conv_f8(A, "t", w, b) if c.kern == "f8" else pack_conv(A, "t", w, b)
+    A.finalize(dev)
+    cw.w = A[cw.w]
+    cw.b = A[cw.b] if cw.b is not None else None
+    if c.kern == "f8":
+        cw.wscale = A[cw.wscale]
+    cw._arena = A
+    assert cw.ci_pad == lin_ci_pad(c), (cw.ci_pad, lin_id(c))
+    if key is not None:
+        LIN_PACKED[dev, key] = cw
+    return cw
+
+
+def lin_onehot(c, m, dev="cpu"):
+    """the packed one-hot weight of column block m (value 448 for fp8: quantize_f8_cols then gives column scale exactly
+    1.0 and code 448)"""
+    v = 448.0 if c.kern == "f8" else 1.0
+    return lin_pack(c, delta_weights(c.Co, c.Ci, 1, 0, m)[:, :, 0] * v, None, (c.kern == "f8", c.Co, c.Ci, m), dev)
+
+
+def lin_make_x(c, seed=0):
+    """host operand of a case -> (x as stored [B, T, Ci], x_scale [B T] | None, the staged operand the kernel must form,
+    fp32: x (bf16), bf16(0.5 x) (fp32 rows, cscale 0.5: exact), code x_scale (fp8; the one-hot 448 is the caller's);
+    None for a general cscale)"""
+    if c.kern == "f8":
+        codes, sx = e4m3_case(c.B, c.T, c.Ci, seed)
+        return codes, sx, e4m3_value(codes) * sx.view(c.B, c.T, 1)
+    g = torch.Generator().manual_seed(seed + c.B * c.T + c.Ci)
+    x = torch.randn(c.B, c.T, c.Ci, generator=g)
+    if c.idt == "bf16":
+        x = bf(x)
+        return x, None, x
+    return x, None, bf(x * c.cscale) if c.cscale == 0.5 else None
+
+
+def lin_x_layout(c, x, poisoned, dev="cpu"):
+    """x on `dev` -> (buffer, Act): poisoned = channel-offset inside a wider, longer buffer of finite poison (2^100; fp8:
+    the code 0x7E), bsx != T ldx; else compact and zero padded"""
+    dt = LIN_DT[c.idt]
+    fill = (LIN_POISON_F8 if poisoned else 0) if c.kern == "f8" else (LIN_POISON if poisoned else 0.0)
+    xb, xa = guarded((c.B, c.T, c.Ci), lin_x_pads(c, poisoned), fill, dt, dev)
+    if c.kern == "f8":
+        xa.t.view(torch.uint8)[:, :, xa.c0:xa.c0 + c.Ci] = x.to(dev)
+    else:
+        xa.t[:, :, xa.c0:xa.c0 + c.Ci] = x.to(dev, dt)
+    assert xa.c0 + lin_ci_pad(c) <= xa.ld and (not poisoned or xa.bs != c.T * xa.ld)
+    return xb, xa
+
+
+def lin_y_layout(c, poisoned, dev="cpu"):
+    """the output -> (buffer, Act): NaN-sentinel filled and guarded by the case's ypads, or compact zeros"""
+    dt = LIN_DT[c.odt]
+    if poisoned:
+        return guarded((c.B, c.T, c.Co), c.ypads, LIN_SENT[dt], dt, dev)
+    return guarded((c.B, c.T, c.Co), (0, 0, 0), 0.0, dt, dev)

@@ -80,3 +80,34 @@ def test_synth_trace_matches_engine_launch_count(tmp_path):
         assert int(r["engine.launches"]) == int(r["launching_calls"]) > 0, r
         assert int(r["kernels"]) >= int(r["launching_calls"]), r
     assert "L ? " not in open(tmp_path / "synth.txt").read()
+
+
+def test_linear_probe_cases_launch_what_the_gpu_test_claims(tmp_path):
+    """the identity-probe table of tests/test_gpu_linear_probe.py (refops.linear_cases) through the engine's routing and
+    the real dispatch: each case launches exactly one kernel of the family it names -- gemm_glds 64-row against 128-row
+    told apart by grid.x and the LDS bytes, gemm_rows / rows16 by name -- with the grid refops.lin_expected_launch
+    restates and grid.z = its K slices.  The stand-in reports 256 CUs, so refops.gemm_tile_rows (the launcher's tile
+    rule, restated for the GPU test) is compared with the launcher's own choice on every gemm_glds case."""
+    import dispatch_trace as D
+    import refops as R
+    _run(tmp_path, "--linear-cases", "--out", tmp_path / "lin.txt")
+    entries = {label: (rc, lines) for _, label, rc, lines in D.parse(tmp_path / "lin.txt")}
+    cases = R.linear_cases(256)
+    assert len(entries) == len(cases) > 100
+    assert any(c.kern == "glds128" for c in cases), "no 128-row-tile case at 256 CUs"
+    lds = {}
+    for c in cases:
+        rc, lines = entries[R.lin_id(c)]
+        launches = [ln.split() for ln in lines if ln.startswith("L ")]
+        assert rc == 0 and len(launches) == 1, (R.lin_id(c), rc, lines)
+        name, grid, nlds = launches[0][1], tuple(int(v) for v in launches[0][2:5]), int(launches[0][8])
+        want, gx, gy, gz = R.lin_expected_launch(c)
+        assert want in name and sum(k in name for k in ("gemm_glds", "gemm_rows", "rows16", "ln_rows")) == 1, (R.lin_id(c), name)
+        assert grid == (gx, gy, gz), (R.lin_id(c), grid, (gx, gy, gz))
+        if want == "gemm_glds":
+            tile = 64 if c.Z > 1 else R.gemm_tile_rows(c.B * c.T, (c.Co + 127) // 128 * 128, 256)
+            assert tile == (128 if c.kern == "glds128" else 64), R.lin_id(c)
+            lds.setdefault(tile, set()).add(nlds)
+        else:
+            assert nlds <= 16 * 1024, (R.lin_id(c), nlds)  # (static LDS only)
+    assert len(lds[64]) == len(lds[128]) == 1 and max(lds[64]) < min(lds[128]) <= LDS_MAX, lds

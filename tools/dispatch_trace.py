@@ -9,6 +9,7 @@ route every traced call to the same kernels with the same launch geometry: the c
     python tools/dispatch_trace.py --sweep --out b.txt               # generated argument structs, valid and broken
     python tools/dispatch_trace.py --objects OTHER/build --lib /tmp/o.so --sweep --out c.txt     # another build
     python tools/dispatch_trace.py --coverage a.txt b.txt            # registered conv-family kernels never launched
+    python tools/dispatch_trace.py --linear-cases --out d.txt        # the identity-probe table of the linears' GPU test
 
 Trace lines (hip_record.cpp): "L kernel gx gy gz bx by bz lds", "A kernel attribute value" (hipFuncSetAttribute),
 "C memcpy|memset bytes", "M text" (this driver's markers: "case NAME" before a synthesis case, "call LABEL" / "rc N"
@@ -478,6 +479,31 @@ def sweep(lib, out):
     print(f"sweep: {len(rcs)} calls, {ok} accepted, {len(rcs) - ok} rejected -> {out}")
 
 
+# ---- mode (c): the linears' probe table -----------------------------------------------------------------------------
+def linear_cases(lib, out):
+    """every case of tests/refops.py linear_cases() (the table tests/test_gpu_linear_probe.py runs on the device) through
+    the engine's routing and the native dispatch, with the operands the GPU test builds (on the host): one "call
+    <case id>" marker per case, then the launch it made"""
+    L = _load(lib, out)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import refops as R
+    from stzs.engine import StyleTTSZS
+    from stzs.params import init_params
+    from stzs.spec import SPEC_TINY
+    eng = StyleTTSZS(SPEC_TINY, init_params(SPEC_TINY, 0), device="cpu")
+    eng.stream = lambda: C.c_void_p(0)  # (no device: the null stream, as tools/launch_trace.py)
+    cases = R.linear_cases(256)  # (the stand-in reports 256 CUs)
+    for c in cases:
+        x, sx, _ = R.lin_make_x(c)
+        _, xa = R.lin_x_layout(c, x, True)
+        _, ya = R.lin_y_layout(c, True)
+        cw = R.lin_onehot(c, 0)
+        L.hip_record_mark(f"call {R.lin_id(c)}".encode())
+        R.lin_launch(eng, c, cw, xa, ya, x_scale=sx)
+        L.hip_record_mark(b"rc 0")
+    print(f"linear cases: {len(cases)} -> {out}")
+
+
 # ---- coverage -----------------------------------------------------------------------------------------------------
 def registered(objdir, names=CONV_OBJECTS):
     """{object: set of registered kernel names}, from the objects' host stubs (nm)"""
@@ -518,6 +544,7 @@ def main():
     g.add_argument("--synth", choices=("tiny", "v0"))
     g.add_argument("--sweep", action="store_true")
     g.add_argument("--coverage", nargs="+", metavar="TRACE")
+    g.add_argument("--linear-cases", action="store_true")
     a = ap.parse_args()
     if a.coverage:
         return coverage(a.objects, a.coverage)
@@ -525,6 +552,8 @@ def main():
     out = os.path.abspath(a.out)
     if a.synth:
         synth(a.synth, lib, out)
+    elif a.linear_cases:
+        linear_cases(lib, out)
     else:
         sweep(lib, out)
 
