@@ -144,9 +144,27 @@ typedef struct stzs_conv_args {
      * vector epilogue (Co, ldy, bsy, ldr, bsr, lda, bsa multiples of 8).  Honoured by the generic conv (flags 0 but
      * STZS_CONV_LINEAR_IDS; x and y both bf16 or both fp32; prologue activation NONE or LEAKY) and by the
      * register-direct k3 LeakyReLU / identity form (STZS_CONV_W_FRAG32, ks 3, no acc_in: narrow at 128- and 64-row
-     * tiles, and wide); every other form returns STZS_EINVAL before any HIP call, stzs_conv1d_group likewise. */
+     * tiles, and wide); every other form returns STZS_EINVAL before any HIP call, stzs_conv1d_group likewise.
+     * All of the above is t_lens_rows = 0.
+     * t_lens_rows = 1 (the ragged decoder): t_lens[b] is utterance b's OWN row count on this launch's input time
+     * axis, T_b = clamp(t_lens[b], 1, T_in); t_lens_mul must be 0 or 1.  The same four rules -- staged rows >= T_b are
+     * zeros after the prologue (Snake(AdaIN(0)) is not 0: the mask covers every tap of the dilated halo, rows shorter
+     * than the halo included), load addresses of x, res and acc_in clamp into the row, the interior fast path tests
+     * against T_b, fused statistics take stored rows < T_b only -- honoured by instances of their own of three forms:
+     *  - the register-direct Snake convs (STZS_CONV_W_FRAG32, Snake prologue, ks 3 / 7 / 11, res_tdiv 1, with or
+     *    without res, acc_in, alpha: single-chunk, multi-chunk narrow and wide, all at 128-row tiles -- a launch may
+     *    take 128-row tiles where the uniform launch would take 64-row ones; every tile form is bit-identical);
+     *  - the polyphase ConvTranspose (STZS_CONV_W_FRAG32, ups > 0, with or without res or STZS_CONV_UPS_NOISE): T_b
+     *    counts INPUT rows, staged input rows q >= T_b are zeros, residual / harmonic-source row loads clamp to the
+     *    utterance's own T_b * ups + refl output rows; y rows t < T_b * ups + refl are the utterance's alone;
+     *  - the narrow conv (STZS_CONV_W_NARROW32, conv_post): staged rows >= T_b are zeros.
+     * Every other form or combination with t_lens_rows = 1 (the generic conv, LANE16, the precise forms, split-K,
+     * pro_part, a plain linear, t_lens_mul 2, the LeakyReLU / identity block form) and any other value of
+     * t_lens_rows returns STZS_EINVAL before any HIP call; stzs_conv1d_group runs problems with lengths one
+     * stzs_conv1d at a time (the trio and pair launches stay length-free).  t_lens_rows != 0 with t_lens NULL:
+     * STZS_EINVAL. */
     const int32_t* t_lens;
-    int32_t t_lens_mul, pad_tl;
+    int32_t t_lens_mul, t_lens_rows;
 } stzs_conv_args;
 /* split-K workspace of a linear over `rows` flat rows: fp32 slab bytes; the tile (= counter) count is
  * bytes / (splitk * 32768).  0 for a bad argument. */
@@ -503,7 +521,12 @@ int stzs_f0n_down(const stzs_f0n_args* a, void* stream);
  * Accepted: nh <= 64, n_fft <= 64, ldh >= 2 * (n_fft/2 + 1), and (hop_s * 255 + n_fft - 2) / hop + 2 <= 8 (the
  * 80-fps frames that the samples of one workgroup's 256 STFT frames can span: hop >= 185 at n_fft 20 / hop_s 5).
  * Every check precedes the first launch: a call that returns an error has run nothing and left `prefix` and `har`
- * untouched. */
+ * untouched.
+ * lens (optional, NULL = the call as before; the ragged decoder): int32 [B] on the device, the 80-fps frames of
+ * utterance b, clamped into [1, T80]: N_b = lens[b] * hop samples, the centre=True reflection at the right edge folds
+ * at the utterance's own N_b, Tf_b = N_b / hop_s + 1; har rows f < Tf_b are the bits of the utterance alone at
+ * T80 = lens[b], rows Tf_b <= f < Tf (all ldh columns) are written as exact zeros on every call -- the zero padding
+ * the noise convs see at an utterance's end; f0[b, lens[b]:] is not read, prefix[b, :, lens[b]:] not written. */
 typedef struct stzs_source_args {
     const float* f0;
     const uint32_t* seeds;
@@ -514,6 +537,7 @@ typedef struct stzs_source_args {
     int32_t B, T80, hop, n_fft, hop_s, nh;
     float sr, sine_amp, noise_std, voiced_thr;
     int32_t har_dtype, pad_i; /* dtype of har: STZS_BF16 | STZS_F32 */
+    const int32_t* lens;
 } stzs_source_args;
 int stzs_harmonic_source(const stzs_source_args* a, void* stream);
 
@@ -522,12 +546,18 @@ int stzs_harmonic_source(const stzs_source_args* a, void* stream);
  * Accepted geometries (stzs_istft and stzs_istft_stream): n_fft is 16 or 20, 1 <= hop_s < n_fft, Tf >= 2.
  * hop_s == n_fft is refused (STZS_ESHAPE): the periodic Hann window's first tap is 0, so the samples f * n_fft would
  * have a zero envelope (torch.istft refuses it too).  The phase argument p is reduced with a two-constant 2 pi that is
- * exact for |p| < 2^17. */
+ * exact for |p| < 2^17.
+ * lens (optional, NULL = the call as before; the ragged decoder; stzs_istft only, the streaming entry points are not
+ * ragged): int32 [B] on the device, the frames Tf_b of utterance b, clamped into [2, Tf]: its last frame, the padded
+ * sample bound and the window-square envelope are those of Tf_b -- wav[b, n < (Tf_b - 1) * hop_s] are the bits of the
+ * utterance alone at Tf = Tf_b, the samples from there to (Tf - 1) * hop_s are stored as exact zeros, post rows
+ * >= Tf_b are not read. */
 typedef struct stzs_istft_args {
     const float* post;
     float* wav;
     int64_t ldp, bsp, bsw;
     int32_t B, Tf, n_fft, hop_s;
+    const int32_t* lens;
 } stzs_istft_args;
 int stzs_istft(const stzs_istft_args* a, void* stream);
 
@@ -698,6 +728,18 @@ typedef struct stzs_copy_args {
     const int32_t* dst_row_off;
 } stzs_copy_args;
 int stzs_copy2d(const stzs_copy_args* a, void* stream);
+/* the ragged decoder's row-count arrays, one small launch per decode: out[k * B + b] = clamp(lens[b], 1, T) * mul[k] +
+ * add[k] for k < n <= 8 (the product in 64 bits, the result saturated to int32): from the alignment's 40-fps frame
+ * counts the 80-fps rows (mul 2), the rows of generator stage i (2 prod r_j, + 1 behind the last stage's reflection
+ * pad) and the iSTFT frame count, each read by stzs_conv_args.t_lens (t_lens_rows 1), stzs_stats_args.lens,
+ * stzs_source_args.lens or stzs_istft_args.lens.  mul and add travel by value (no device table to keep alive). */
+typedef struct stzs_frame_rows_args {
+    const int32_t* lens; /* int32 [B] on the device */
+    int32_t* out;        /* int32 [n][B] */
+    int32_t B, T, n, pad_i;
+    int32_t mul[8], add[8];
+} stzs_frame_rows_args;
+int stzs_frame_rows(const stzs_frame_rows_args* a, void* stream);
 /* token embedding gather: y[b, t, :] = emb[tok[b, t], :] (f32 table -> bf16 rows) */
 int stzs_embed(const int32_t* tok, const float* emb, void* y, int B, int T, int D, int64_t ldy,
                void* stream);

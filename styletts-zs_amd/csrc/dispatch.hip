@@ -28,7 +28,16 @@ __attribute__((visibility("hidden"))) int stzs_conv_check(const stzs_conv_args* 
     if (a->pro_act == STZS_ACT_SNAKE && !a->pro_alpha) return STZS_EINVAL;
     if (a->stat_part && !stzs_aligned(a->stat_part, 8)) return STZS_EINVAL;
     if (a->splitk > 1 && !f.splitk) return STZS_EINVAL;
-    if (a->t_lens) {
+    if (a->t_lens_rows != 0 && (a->t_lens_rows != 1 || !a->t_lens)) return STZS_EINVAL;
+    if (a->t_lens && a->t_lens_rows == 1) {
+        // the ragged decoder: t_lens[b] is the utterance's own row count on this launch's input time axis.  A form
+        // with such kernels, bf16 rows, stride 1, per-utterance tiles (not a plain linear), no split-K, no pro_part,
+        // no multiplier; row for row, or the polyphase ConvTranspose's T_in + 1 GEMM rows (each launcher: the rest)
+        if (!f.t_rows || (a->flags & STZS_CONV_A_DMA) || a->stride != 1 || a->splitk > 1 || a->pro_part ||
+            stzs_plain_linear(*a) || a->in_dtype != STZS_BF16 || a->t_lens_mul < 0 || a->t_lens_mul > 1 ||
+            (a->ups > 0 ? a->T_out != a->T_in + 1 : (a->ups != 0 || a->T_out != a->T_in)) || !stzs_aligned(a->t_lens, 4))
+            return STZS_EINVAL;
+    } else if (a->t_lens) {
         // ragged frame batch: a form with length-aware kernels (the generic one: not its LDS-DMA GEMM), row for row
         // (stride 1, T_out == T_in, no ConvTranspose), per-utterance tiles (not a plain linear), no split-K, the
         // prologue statistics finalised (no pro_part)

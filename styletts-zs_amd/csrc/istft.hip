@@ -31,6 +31,9 @@ struct IstftJob {
     float* wav;            // wav[b * bsw + n - n0]
     long ldp, bsp, bsw, ldt, n0, m_end;  // m_end: exclusive padded-sample bound of the chunk
     int B, f0, Fc, hs;
+    // a ragged batch (stzs_istft only: the whole utterance, f0 = 0, final): frames per utterance, clamped into [2, Fc];
+    // utterance b's last frame and sample bound are those of its own count, the samples up to m_end stored as zeros
+    const int32_t* lens;
 };
 
 STZS_DEV int halo_of(int nfft, int hs) { return (nfft + hs - 1) / hs - 1; }
@@ -48,7 +51,13 @@ __global__ __launch_bounds__(256) void istft_kernel(const IstftJob a) {
     float* win = tws + nfft;
     const int b = blockIdx.y, tid = threadIdx.x;
     const int fb0 = a.f0 + blockIdx.x * FB;  // absolute first frame of this block
-    const int flast = a.f0 + a.Fc - 1;       // last frame of the chunk
+    int flast = a.f0 + a.Fc - 1;             // last frame of the chunk
+    long m_end = a.m_end;
+    if (a.lens) {  // (uniform per workgroup; f0 = 0)
+        const int v = a.lens[b];
+        flast = (v < 2 ? 2 : (v > a.Fc ? a.Fc : v)) - 1;
+        m_end = (long)flast * hs + nfft / 2;
+    }
     if (tid < nfft) {
         const double ang = 2.0 * 3.141592653589793 * tid / nfft;
         twc[tid] = (float)cos(ang);
@@ -112,6 +121,10 @@ __global__ __launch_bounds__(256) void istft_kernel(const IstftJob a) {
         const long m = (long)fb0 * hs + s;  // padded sample index
         const long n = m - nfft / 2;        // output sample index (centre trim)
         if (n < a.n0 || m >= a.m_end) continue;
+        if (m >= m_end) {  // a ragged batch: past the utterance's own last sample
+            W[n - a.n0] = 0.f;
+            continue;
+        }
         float y = 0.f, env = 0.f;
         int fhi = (int)(m / hs);
         if (fhi > flast) fhi = flast;
@@ -163,10 +176,11 @@ bool bad_size(int nfft) { return nfft != 16 && nfft != 20; }  // the instantiate
 }  // namespace
 
 extern "C" int stzs_istft(const stzs_istft_args* a, void* stream) {
-    if (!a || !a->post || !a->wav) return STZS_EINVAL;
+    if (!a || !a->post || !a->wav || !stzs_aligned(a->lens, 4)) return STZS_EINVAL;
     if (a->B <= 0 || a->Tf < 2 || bad_geom(a->n_fft, a->hop_s) || bad_size(a->n_fft) || a->ldp < a->n_fft + 2)
         return STZS_ESHAPE;
     IstftJob j{};
+    j.lens = a->lens;
     j.post = a->post;
     j.wav = a->wav;
     j.ldp = a->ldp;

@@ -6,6 +6,7 @@
 //   stzs_mean_rows    pooled style / prompt vectors
 //   stzs_copy2d       strided row copy with dtype conversion (buffer assembly, no torch ops)
 //   stzs_embed        token embedding rows (text front end)
+//   stzs_frame_rows   the ragged decoder's per-stage row counts from the alignment's frame counts
 #include "common.hpp"
 #include "cfg.hpp"
 
@@ -53,6 +54,16 @@ __global__ void state_init_kernel(float* x, const float* eps, int B, int N, int 
     const float v = eps[i] * sigma;
     x[i] = v;
     if (cfg) x[(long)B * N + i] = v;
+}
+
+// out[k][b] = clamp(lens[b], 1, T) * mul[k] + add[k]: the ragged decoder's row counts per stage (the clamp first, the
+// arithmetic in 64 bits, the result saturated: a garbage length never wraps into range)
+__global__ void frame_rows_kernel(const stzs_frame_rows_args a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.B * a.n) return;
+    const int k = i / a.B, b = i - k * a.B;
+    const long v = (long)rag_rows(a.lens, b, 1, a.T) * a.mul[k] + a.add[k];
+    a.out[i] = v > 0x7fffffffL ? 0x7fffffff : (v < -0x7fffffffL - 1 ? -0x7fffffff - 1 : (int)v);
 }
 
 __global__ void mean_rows_kernel(const float* x, float* y, int B, int L, long ldx, long bsx, int c0, int C,
@@ -181,6 +192,13 @@ extern "C" int stzs_copy2d(const stzs_copy_args* a, void* stream) {
         return stzs_launch((copy_kernel<bf16_t, float>), g, dim3(256), 0, s, *a);
     else
         return STZS_EDTYPE;
+}
+
+extern "C" int stzs_frame_rows(const stzs_frame_rows_args* a, void* stream) {
+    if (!a || !a->lens || !a->out || !stzs_aligned(a->lens, 4) || !stzs_aligned(a->out, 4)) return STZS_EINVAL;
+    if (a->B <= 0 || a->T <= 0 || a->n <= 0 || a->n > 8) return STZS_ESHAPE;
+    return stzs_launch(frame_rows_kernel, dim3(nblk((long)a->B * a->n)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), *a);
 }
 
 extern "C" int stzs_embed(const int32_t* tok, const float* emb, void* y, int B, int T, int D, int64_t ldy,

@@ -388,6 +388,9 @@ constexpr int NBT = 256;
 constexpr int NSLOT_B = 2048;
 constexpr int NSB = 9;  // staged vectors per thread per batch (two batches: 16 x 18 = 288 rows)
 
+// RAG (stzs_conv_args.t_lens with t_lens_rows 1, the ragged decoder; an instance of its own): utterance bq's own row
+// count stands in for T_in in the staging clamp and the zero-padding mask.
+template <bool RAG>
 __global__ __launch_bounds__(NTH, 2) void narrow_conv(const stzs_conv_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int ks = a.ks, dil = a.dil;
@@ -398,6 +401,7 @@ __global__ __launch_bounds__(NTH, 2) void narrow_conv(const stzs_conv_args a) {
     const int bx = (a.flags & STZS_CONV_LINEAR_IDS) ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
     const int bq = bx / tpb;
     const int t0 = (bx - bq * tpb) * NBT;
+    const int Tin = RAG ? rag_rows(a.t_lens, bq, 1, a.T_in) : a.T_in;  // (uniform per workgroup)
     const int nchunk = a.ci_pad >> 7;
     const int NK = nchunk * ks * 4;
     const bf16_t* Wt = reinterpret_cast<const bf16_t*>(a.w);
@@ -452,7 +456,7 @@ __global__ __launch_bounds__(NTH, 2) void narrow_conv(const stzs_conv_args a) {
 #pragma unroll
             for (int i = 0; i < NSB; ++i) {
                 int tin = t0 - a.pad + rsub + 16 * (bt * NSB + i);
-                tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+                tin = tin < 0 ? 0 : (tin >= Tin ? Tin - 1 : tin);
                 raw[i] = *reinterpret_cast<const uint4*>(X + (long)tin * a.ldx + cl);
             }
 #pragma unroll
@@ -460,7 +464,7 @@ __global__ __launch_bounds__(NTH, 2) void narrow_conv(const stzs_conv_args a) {
                 const int r = rsub + 16 * (bt * NSB + i);
                 if (r < rows_in) {
                     const int tin = t0 - a.pad + r;
-                    const bool ok = c_ok && tin >= 0 && tin < a.T_in;
+                    const bool ok = c_ok && tin >= 0 && tin < Tin;
                     float f[8];
                     unpack8(raw[i], f);
 #pragma unroll
@@ -584,5 +588,6 @@ __attribute__((visibility("hidden"))) int stzs_narrow_conv_launch(const stzs_con
         return STZS_ESHAPE;
     const size_t lds = (((size_t)rows_in * P + 15) & ~(size_t)15) + NSL * NSLOT_B;
     dim3 grid((unsigned)a.B * (unsigned)((a.T_out + NBT - 1) / NBT));
-    return stzs_launch(narrow_conv, grid, dim3(NTH), lds, s, a);
+    if (a.t_lens && a.t_lens_rows != 1) return STZS_EINVAL;  // (stzs_conv_check: only an utterance's own row count)
+    return stzs_launch(a.t_lens ? narrow_conv<true> : narrow_conv<false>, grid, dim3(NTH), lds, s, a);
 }

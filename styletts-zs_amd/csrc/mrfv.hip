@@ -1,5 +1,7 @@
 // The MRF conv, register-direct weight form: the launcher (stzs_mrfv_conv_launch) and the
-// multi-chunk instances -- the wide stage-0 forms and the decoder / predictor AdaIN-block k3 convs.  The kernel template
+// multi-chunk instances -- the wide stage-0 forms, the decoder / predictor AdaIN-block k3 convs and the length-aware
+// (RAG) instances of both: the block forms' for ragged frame batches, the Snake forms' for the ragged decoder
+// (stzs_conv_args.t_lens, t_lens_rows 0 / 1).  The kernel template
 // and its design notes: csrc/mrfv_kernel.hpp; the single-chunk stage-1 instances: csrc/mrfv_n1.hip.
 #include "mrfv_kernel.hpp"
 
@@ -27,6 +29,11 @@ int mrfv_shape(const stzs_conv_args& a) {
     if (a.in_dtype == STZS_F8 || a.x_scale) return STZS_EDTYPE;
     if (!stzs_aligned(a.y, 16)) return STZS_EINVAL;
     if (a.ups > 0) return STZS_OK;  // (the ConvTranspose form: csrc/ups.hip checks the rest)
+    // the ragged decoder (t_lens_rows 1): the Snake convs only, with one of the generator's four epilogue combinations
+    // (pick_rag, csrc/mrfv_kernel.hpp) -- the block forms keep the §2d rule below
+    if (a.t_lens && a.t_lens_rows == 1 &&
+        (a.pro_act != STZS_ACT_SNAKE || (a.ks != 3 && a.ks != 7 && a.ks != 11) || (!a.res && (a.acc_in || a.alpha != 1.f))))
+        return STZS_EINVAL;
     const int rows_in = 128 + (a.ks - 1) * a.dil;
     if (a.stride != 1 || a.cic != 128 || a.ci_pad % 128 || a.Co % 8 || rows_in > 16 * sb_rows(a.ks) ||
         a.in_dtype != STZS_BF16 || a.out_dtype != STZS_BF16 || a.gate || a.epi_act != STZS_ACT_NONE || a.ups ||
@@ -35,7 +42,8 @@ int mrfv_shape(const stzs_conv_args& a) {
         return STZS_ESHAPE;
     if (a.pro_act == STZS_ACT_SNAKE && a.res && a.res_tdiv != 1) return STZS_ESHAPE;  // (TD1 in the kernel)
     // ragged frame batch (t_lens): the k3 LeakyReLU / identity block convs only (stzs_conv_check: the rest of the rule)
-    if (a.t_lens && (a.ks != 3 || a.acc_in || (a.pro_act != STZS_ACT_LEAKY && a.pro_act != STZS_ACT_NONE)))
+    if (a.t_lens && a.t_lens_rows == 0 &&
+        (a.ks != 3 || a.acc_in || (a.pro_act != STZS_ACT_LEAKY && a.pro_act != STZS_ACT_NONE)))
         return STZS_EINVAL;
     return STZS_OK;
 }
@@ -108,7 +116,14 @@ __attribute__((visibility("hidden"))) int stzs_mrfv_conv_launch(const stzs_conv_
     bool wide, t64;
     mrfv_tiles(a, wide, t64);
     mrfv_kfn k = nullptr;
-    if (a.pro_act == STZS_ACT_SNAKE) {
+    if (a.pro_act == STZS_ACT_SNAKE && a.t_lens) {
+        // (mrfv_shape: t_lens_rows 1) the ragged decoder's instances, all at 128-row tiles: single-chunk, wide where the
+        // uniform launch would be wide, else narrow -- every tile form is bit-identical
+        t64 = false;
+        const bool al = a.alpha != 1.f;
+        k = a.ci_pad == 128 ? stzs_mrfv_pick_n1_rag(a.ks, R, A, al)
+                            : wide ? pick_rag<0, 2>(a.ks, R, A, al) : pick_rag<0, 1>(a.ks, R, A, al);
+    } else if (a.pro_act == STZS_ACT_SNAKE) {
         const bool one = a.ci_pad == 128;
         const bool al = a.alpha != 1.f;
         k = R ? (A ? pick<STZS_ACT_SNAKE, true, true>(a.ks, one, al, wide, t64) : pick<STZS_ACT_SNAKE, true, false>(a.ks, one, al, wide, t64))

@@ -117,9 +117,14 @@ __device__ unsigned long long g_mprof[8 * 16384];
 // their own -- the Snake forms and every kernel without the lengths are unchanged): utterance bq's own row count Tin
 // (clamped into [1, T_in]) stands in for T_in in the staging clamps, the zero-padding mask and the interior test, and
 // in the epilogue's residual clamp and statistics mask.
+// RAG on the Snake forms (t_lens_rows = 1, the ragged decoder; 128-row tiles: single-chunk, multi-chunk narrow, wide):
+// the same sites -- the zero mask sits behind the Snake transform for every staged row, the dilated halo included (an
+// utterance shorter than the halo: every row past it is zero), the single-chunk form's early row loads and the
+// accumulate-input loads clamp into the utterance as the others do.
 template <int PACT, bool HR, bool HA, int KS, int NCH, bool AL, int WPW = 1, int BT = 128, bool RAG = false>
 STZS_DEV void mrfv_body(const stzs_conv_args a) {
-    static_assert(!RAG || (PACT != STZS_ACT_SNAKE && !HA && KS == 3 && NCH == 0), "ragged rows: the k3 block convs");
+    static_assert(!RAG || (PACT != STZS_ACT_SNAKE && !HA && KS == 3 && NCH == 0) || (PACT == STZS_ACT_SNAKE && BT == 128),
+                  "ragged rows: the k3 block convs, the Snake convs at 128-row tiles");
     static_assert(WPW == 1 || (WPW == 2 && NCH != 1), "the wide form is for multi-chunk inputs");
     static_assert(BT == 128 || (BT == 64 && WPW == 1), "64-row tiles: narrow form");
     MPROF(5, __builtin_amdgcn_s_memrealtime())
@@ -225,7 +230,8 @@ STZS_DEV void mrfv_body(const stzs_conv_args a) {
 #pragma unroll
                 for (int i = 0; i < SB; ++i) {
                     int tin = t0 - a.pad + rsub + 16 * i;
-                    tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+                    if constexpr (RAG) tin = tin < 0 ? 0 : (tin >= Tin ? Tin - 1 : tin);
+                    else tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
                     const unsigned off = (unsigned)(tin * (int)a.ldx + cl) * 2u;
 #if defined(STZS_MRFV_PROF) && STZS_MRFV_DIAG == 2
                     rawe[i] = make_uint4(off, off ^ 1u, off ^ 2u, off ^ 3u);  // (probe: no loads, same transform)
@@ -525,6 +531,26 @@ void (*pick_ks(int ks))(stzs_conv_args) {
     }
 }
 
+// the Snake instances of a ragged decoder launch (RAG, 128-row tiles).  Four epilogue combinations, the generator's own:
+// plain (c1), residual (c2), residual + alpha (a stage's last c2 of the first resblock), residual + accumulate input +
+// alpha (of the others; alpha == 1 there multiplies by 1: the same bits).  An accumulate input or alpha != 1 without a
+// residual: nullptr.
+template <bool HR, bool HA, bool AL, int NCH, int WPW>
+void (*pick_rag_ks(int ks))(stzs_conv_args) {
+    switch (ks) {
+        case 3: return mrfv_conv<STZS_ACT_SNAKE, HR, HA, 3, NCH, AL, WPW, 128, true>;
+        case 7: return mrfv_conv<STZS_ACT_SNAKE, HR, HA, 7, NCH, AL, WPW, 128, true>;
+        case 11: return mrfv_conv<STZS_ACT_SNAKE, HR, HA, 11, NCH, AL, WPW, 128, true>;
+        default: return nullptr;
+    }
+}
+template <int NCH, int WPW>
+void (*pick_rag(int ks, bool hr, bool ha, bool al))(stzs_conv_args) {
+    if (!hr) return (ha || al) ? nullptr : pick_rag_ks<false, false, false, NCH, WPW>(ks);
+    if (ha) return pick_rag_ks<true, true, true, NCH, WPW>(ks);
+    return al ? pick_rag_ks<true, false, true, NCH, WPW>(ks) : pick_rag_ks<true, false, false, NCH, WPW>(ks);
+}
+
 }  // namespace
 
 // the narrow single-chunk Snake forms (the stage-1 generator convs, NCH = 1), compiled in csrc/mrfv_n1.hip without
@@ -533,5 +559,6 @@ void (*pick_ks(int ks))(stzs_conv_args) {
 // faster so built (profiles/r06e_mrfv_nopk.log), while the wide stage-0 forms (256 VGPRs) lose 7 % and keep them
 using mrfv_kfn = void (*)(stzs_conv_args);
 mrfv_kfn stzs_mrfv_pick_n1(int ks, bool hr, bool ha, bool al, bool t64);
+mrfv_kfn stzs_mrfv_pick_n1_rag(int ks, bool hr, bool ha, bool al);  // (their ragged decoder instances: pick_rag<1, 1>)
 using mrfv_trio_kfn = void (*)(stzs_conv_args, stzs_conv_args, stzs_conv_args);
 mrfv_trio_kfn stzs_mrfv_trio_pick_n1(bool hr);  // (the single-chunk trio forms, 64-row tiles)

@@ -74,8 +74,10 @@ __global__ __launch_bounds__(256) void phase_prefix_kernel(const stzs_source_arg
     const float* F = a.f0 + (long)b * a.ldf;
     float* P = a.prefix + (long)i * a.T80;
     double acc = 0.0;
-    for (int k0 = 0; k0 < a.T80; k0 += PP_CHUNK) {
-        const int n = min(PP_CHUNK, a.T80 - k0);
+    // (a ragged batch: the utterance's own frames -- the prefix is causal, F0 past them is not read)
+    const int T80b = a.lens ? rag_rows(a.lens, b, 1, a.T80) : a.T80;
+    for (int k0 = 0; k0 < T80b; k0 += PP_CHUNK) {
+        const int n = min(PP_CHUNK, T80b - k0);
         __syncthreads();
         for (int k = threadIdx.x; k < n; k += 256) {
             const double inc = __ddiv_rn(__dmul_rn((double)F[k0 + k], (double)(h + 1)), (double)a.sr);
@@ -112,8 +114,12 @@ __global__ __launch_bounds__(256) void source_stft_kernel(const stzs_source_args
     float* fpre = finc + KW * a.nh;                             // [KW][nh] per-frame phase prefix + ph0
     float* mw = fpre + KW * a.nh;                               // nh merge weights
     const int b = blockIdx.y, f0i = blockIdx.x * FB, tid = threadIdx.x;
-    const int N = a.T80 * a.hop;
+    // a ragged batch (a.lens): N and Tf are the utterance's own -- the right-edge reflection folds at its own last
+    // sample, its frames are the bits of the utterance alone (the same workgroup, 80-fps frames and samples), the
+    // frames from Tf to the padded count TfP are stored as zeros
+    const int N = (a.lens ? rag_rows(a.lens, b, 1, a.T80) : a.T80) * a.hop;
     const int Tf = N / hs + 1;
+    const int TfP = a.T80 * a.hop / hs + 1;
     if (tid < nfft) {
         const double ang = 2.0 * 3.141592653589793 * tid / nfft;
         twc[tid] = (float)cos(ang);
@@ -131,7 +137,8 @@ __global__ __launch_bounds__(256) void source_stft_kernel(const stzs_source_args
     const float* P = a.prefix + (long)b * a.nh * a.T80;
     // the <= KW 80-fps frames this workgroup's samples fall in (reflection maps into them as well)
     const int nlo = max(f0i * hs - nfft / 2, 0), nhi = min(f0i * hs - nfft / 2 + NS - 1, N - 1);
-    const int k_lo = nlo / a.hop, nk = nhi / a.hop - k_lo + 1;
+    // (a ragged batch: a workgroup wholly past the utterance's samples spans no frame and reads no F0)
+    const int k_lo = nlo / a.hop, nk = nhi >= nlo ? nhi / a.hop - k_lo + 1 : 0;
     for (int e = tid; e < nk * a.nh; e += 256) {
         const int kk = e / a.nh, h = e - kk * a.nh, k = k_lo + kk;
         finc[kk * a.nh + h] = __fdiv_rn(__fmul_rn(F[k], (float)(h + 1)), a.sr);
@@ -145,7 +152,8 @@ __global__ __launch_bounds__(256) void source_stft_kernel(const stzs_source_args
         if (n < 0) n = -n;
         if (n >= N) n = 2 * (N - 1) - n;
         float v = 0.f;
-        if (n >= 0 && n < N) {
+        // (n / hop inside the workgroup's nk frames: every sample a stored frame reads is; the others stay 0)
+        if (n >= 0 && n < N && n / a.hop >= k_lo && n / a.hop < k_lo + nk) {
             const int k = n / a.hop, kk = k - k_lo;
             const float jj = (float)(n - k * a.hop + 1);
             const bool voiced = F[k] > a.voiced_thr;
@@ -231,13 +239,18 @@ __global__ __launch_bounds__(256) void source_stft_kernel(const stzs_source_args
             if (f32) Hf[c] = 0.f;
             else Hh[c] = 0;
         }
+    } else if (tid < FB && f < TfP) {  // a ragged batch: the frames past the utterance's own, zeros on every call
+        for (int c = 0; c < a.ldh; ++c) {
+            if (a.har_dtype == STZS_F32) reinterpret_cast<float*>(a.har)[(long)b * a.bsh + (long)f * a.ldh + c] = 0.f;
+            else reinterpret_cast<bf16_t*>(a.har)[(long)b * a.bsh + (long)f * a.ldh + c] = 0;
+        }
     }
 }
 
 }  // namespace
 
 extern "C" int stzs_harmonic_source(const stzs_source_args* a, void* stream) {
-    if (!a || !a->f0 || !a->seeds || !a->merge_w || !a->prefix || !a->har) return STZS_EINVAL;
+    if (!a || !a->f0 || !a->seeds || !a->merge_w || !a->prefix || !a->har || !stzs_aligned(a->lens, 4)) return STZS_EINVAL;
     if (a->B <= 0 || a->T80 <= 0 || a->nh <= 0 || a->nh > 64 || a->n_fft <= 0 || a->n_fft > 64 || a->hop_s <= 0)
         return STZS_ESHAPE;
     if (a->ldh < 2 * (a->n_fft / 2 + 1)) return STZS_ESHAPE;

@@ -34,7 +34,11 @@ constexpr int RING = 4;                   // weight K-steps in flight (3 ahead);
 // NZ (STZS_CONV_UPS_NOISE): the 1x1 noise conv fused as one more K-step per column tile whose B operand is the
 // harmonic-source rows of the tile's output rows (loaded at the tile's start, as the residual rows were) and whose
 // weights follow the tile's ConvTranspose K-steps in the stream; there is then no residual operand.
-template <int NCH, bool HR, bool NZ, int BT = 128>
+// RAG (stzs_conv_args.t_lens with t_lens_rows 1, the ragged decoder; instances of their own, the others compile from the
+// text they had): utterance bq holds Tb = clamp(t_lens[bq], 1, T_in) INPUT rows -- the staging clamps into them and
+// stages rows q >= Tb as zeros (what the utterance alone stages past its end: LeakyReLU(0) = +0), the residual /
+// harmonic-source row loads clamp to its own Tb * ups + refl output rows.
+template <int NCH, bool HR, bool NZ, int BT = 128, bool RAG = false>
 __global__ __launch_bounds__(NTH, NCH * tile_of(BT) <= 80 * 1024 ? 2 : 1) void ups_conv(const stzs_conv_args a, int ctw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int ROWS = rows_of(BT), TILE = tile_of(BT);
@@ -50,6 +54,8 @@ __global__ __launch_bounds__(NTH, NCH * tile_of(BT) <= 80 * 1024 ? 2 : 1) void u
     const int gy = lin / nx, bx = lin - gy * nx;
     const int bq = bx / tpb;
     const int q0 = (bx - bq * tpb) * BT;
+    [[maybe_unused]] int Tb = 0;
+    if constexpr (RAG) Tb = rag_rows(a.t_lens, bq, 1, a.T_in);  // (uniform per workgroup)
     const int ncol = a.ups * a.Co;
     const int nct = (ncol + 127) / 128;
     const int ct0 = gy * ctw, ct1 = min(nct, ct0 + ctw);
@@ -78,14 +84,17 @@ __global__ __launch_bounds__(NTH, NCH * tile_of(BT) <= 80 * 1024 ? 2 : 1) void u
 #pragma unroll
         for (int i = 0; i < SB; ++i) {
             int tin = q0 - 1 + rsub + 16 * i;
-            tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+            if constexpr (RAG) tin = tin < 0 ? 0 : (tin >= Tb ? Tb - 1 : tin);
+            else tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
             raw[i] = *reinterpret_cast<const uint4*>(X + (long)tin * a.ldx + cl);
         }
 #pragma unroll
         for (int i = 0; i < SB; ++i) {
             const int r = rsub + 16 * i;
             const int tin = q0 - 1 + r;
-            const bool ok = c_ok && tin >= 0 && tin < a.T_in;
+            bool ok;
+            if constexpr (RAG) ok = c_ok && tin >= 0 && tin < Tb;
+            else ok = c_ok && tin >= 0 && tin < a.T_in;
             const uint32_t w[4] = {raw[i].x, raw[i].y, raw[i].z, raw[i].w};
             uint32_t o[4];
 #pragma unroll
@@ -105,7 +114,8 @@ __global__ __launch_bounds__(NTH, NCH * tile_of(BT) <= 80 * 1024 ? 2 : 1) void u
     // ---- column tiles over the resident input ----
     const int g = lane >> 4, n = lane & 15;
     const int xoff0 = (lane & 15) * P + (lane >> 4) * 16;
-    const int t_hi = a.T_final + a.refl - 1;
+    int t_hi = a.T_final + a.refl - 1;
+    if constexpr (RAG) t_hi = min(t_hi, Tb * a.ups + a.refl - 1);  // (Tb <= T_in < 2^31 / ups: T_final = T_in ups)
     const bf16_t* Rb = reinterpret_cast<const bf16_t*>(a.res) + (long)bq * a.bsr;
     bf16_t* Y = reinterpret_cast<bf16_t*>(a.y) + (long)bq * a.bsy;
     f32x4 acc[2][MT];
@@ -232,6 +242,7 @@ __attribute__((visibility("hidden"))) int stzs_ups_conv_launch(const stzs_conv_a
     if (nz && (!a.res || !a.gate || a.Co % 128 || a.refl < 0 || a.refl > 1 || a.ldr < 32 || a.ldr % 8 || a.bsr % 8 ||
                (a.refl && a.T_final + a.refl < 3)))
         return STZS_EINVAL;  // fused noise conv: harmonic-source rows (>= 32 channels) + fp32 noise weights required
+    if (a.t_lens && a.t_lens_rows != 1) return STZS_EINVAL;  // (stzs_conv_check: only an utterance's own row count)
     if (a.ks != 2 || a.pad != 1 || a.dil != 1 || a.stride != 1 || a.cic != 128 || a.ci_pad % 128 || a.Co % 32 ||
         a.T_out != a.T_in + 1 || a.in_dtype != STZS_BF16 || a.out_dtype != STZS_BF16 || a.pro_mode != STZS_PRO_NONE ||
         (a.pro_act != STZS_ACT_LEAKY && a.pro_act != STZS_ACT_NONE) || a.pro_cscale != 1.f || (a.gate && !nz) || a.acc_in ||
@@ -246,7 +257,9 @@ __attribute__((visibility("hidden"))) int stzs_ups_conv_launch(const stzs_conv_a
         const char* e = getenv("STZS_UPS_BT");
         return e ? atoi(e) : 0;
     }();
-    const int BT = bt_env == 64 || bt_env == 128 ? bt_env : (nch > 2 ? 64 : 128);
+    // (the ragged decoder's instances exist at the default tile height only: bit-identical either way)
+    const bool rag = a.t_lens != nullptr;
+    const int BT = !rag && (bt_env == 64 || bt_env == 128) ? bt_env : (nch > 2 ? 64 : 128);
     const int nqt = a.B * ((a.T_out + BT - 1) / BT);
     // column tiles per workgroup: all of them (input staged once), unless the q-tile grid alone leaves most of the
     // chip idle (the 40-fps first stage: 128 q tiles at batch 64) -- then slices, ~4 workgroups per CU in total
@@ -260,6 +273,17 @@ __attribute__((visibility("hidden"))) int stzs_ups_conv_launch(const stzs_conv_a
     const bool R = a.res != nullptr;
 #define STZS_UPS_PICK(N, B_)                                                                                    \
     k = nz ? ups_conv<N, false, true, B_> : R ? ups_conv<N, true, false, B_> : ups_conv<N, false, false, B_>;
+#define STZS_UPS_PICK_RAG(N, B_)                                                                                \
+    k = nz ? ups_conv<N, false, true, B_, true> : R ? ups_conv<N, true, false, B_, true> : ups_conv<N, false, false, B_, true>;
+    if (rag) {
+        switch (nch) {
+            case 1: STZS_UPS_PICK_RAG(1, 128) break;
+            case 2: STZS_UPS_PICK_RAG(2, 128) break;
+            case 3: STZS_UPS_PICK_RAG(3, 64) break;
+            case 4: STZS_UPS_PICK_RAG(4, 64) break;
+            default: return STZS_ESHAPE;
+        }
+    } else
     switch (nch * (BT == 64 ? -1 : 1)) {
         case 1: STZS_UPS_PICK(1, 128) break;
         case 2: STZS_UPS_PICK(2, 128) break;
@@ -272,5 +296,6 @@ __attribute__((visibility("hidden"))) int stzs_ups_conv_launch(const stzs_conv_a
         default: return STZS_ESHAPE;
     }
 #undef STZS_UPS_PICK
+#undef STZS_UPS_PICK_RAG
     return stzs_launch(k, dim3((unsigned)nqt, (unsigned)groups), dim3(NTH), lds, s, a, ctw);
 }

@@ -57,7 +57,8 @@ class ConvArgs(C.Structure):
                [("stat_part", vp), ("stat_ld", i64), ("x_scale", vp), ("w_scale", vp),
                 ("splitk_ws", vp), ("splitk_ctr", vp), ("splitk", i32), ("pad_sk", i32),
                 ("pro_part", vp), ("pro_ld", i64), ("pro_nch", i32), ("pro_T", i32), ("pro_eps", f32), ("pad_pp", f32),
-                ("t_lens", opt_vp), ("t_lens_mul", i32), ("pad_tl", i32)]  # ragged frame batch: rows per utterance
+                ("t_lens", opt_vp), ("t_lens_mul", i32), ("t_lens_rows", i32)]  # ragged frame batch: rows per utterance
+    # (t_lens_rows 0: t_lens in 40-fps frames, x t_lens_mul; 1: the utterance's own rows on this launch's time axis)
 
 
 class StatsArgs(C.Structure):
@@ -136,12 +137,19 @@ class SourceArgs(C.Structure):
                [(n, i64) for n in ("ldf", "ldh", "bsh")] + \
                [(n, i32) for n in ("B", "T80", "hop", "n_fft", "hop_s", "nh")] + \
                [(n, f32) for n in ("sr", "sine_amp", "noise_std", "voiced_thr")] + \
-               [("har_dtype", i32), ("pad_i", i32)]
+               [("har_dtype", i32), ("pad_i", i32), ("lens", opt_vp)]  # lens: optional int32 [B], 80-fps frames per utterance
 
 
 class IstftArgs(C.Structure):
     _fields_ = [("post", vp), ("wav", vp), ("ldp", i64), ("bsp", i64), ("bsw", i64),
-                ("B", i32), ("Tf", i32), ("n_fft", i32), ("hop_s", i32)]
+                ("B", i32), ("Tf", i32), ("n_fft", i32), ("hop_s", i32),
+                ("lens", opt_vp)]  # optional int32 [B]: frames per utterance
+
+
+class FrameRowsArgs(C.Structure):
+    """stzs_frame_rows: out[k, b] = clamp(lens[b], 1, T) * mul[k] + add[k], k < n <= 8"""
+    _fields_ = [("lens", vp), ("out", vp), ("B", i32), ("T", i32), ("n", i32), ("pad_i", i32),
+                ("mul", i32 * 8), ("add", i32 * 8)]
 
 
 class IstftStreamArgs(C.Structure):
@@ -242,7 +250,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
            "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_mask_rows", "stzs_code_quantize",
            "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler",
-           "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
+           "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_frame_rows", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
 
 _lib = None
@@ -307,6 +315,7 @@ def load():
         "stzs_state_init": ([vp, vp, i32, i32, i32, f32, vp], i32),
         "stzs_mean_rows": ([vp, vp, i32, i32, i64, i64, i32, i32, i64, vp], i32),
         "stzs_copy2d": ([P(CopyArgs), vp], i32),
+        "stzs_frame_rows": ([P(FrameRowsArgs), vp], i32),
         "stzs_embed": ([vp, vp, vp, i32, i32, i32, i64, vp], i32),
         "stzs_embed_f32": ([vp, vp, vp, i32, i32, i32, i64, vp], i32),
         "stzs_embed_lens": ([vp, vp, vp, vp, i32, i32, i32, i64, i32, vp], i32),

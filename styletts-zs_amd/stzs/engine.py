@@ -485,7 +485,7 @@ class StyleTTSZS:
              pro_slope=0.0, pro_alpha=None, cscale=1.0, res: Act = None, res_tdiv=1, acc_in: Act = None,
              alpha=1.0, beta=0.0, gate=None, gate_bs=0, epi_act=L.ACT_NONE, epi_slope=0.0, ups_pad=0,
              T_final=0, refl=0, flags=0, stats_key=None, x_scale=None, post_ln=None, pre_ln=None, splitk=0, rows=0,
-             attn=None, collect=None, t_lens=None, t_lens_mul=1, what="conv"):
+             attn=None, collect=None, t_lens=None, t_lens_mul=1, t_lens_rows=0, what="conv"):
         """-> y, or (y, (mean, rstd, stat_bs)) with stats_key: InstanceNorm statistics of the stored
         output fused into the conv epilogue (per-tile partials) + one small finalize launch.
         collect (a list): append the conv's stzs_conv_args to it instead of launching (the caller launches the
@@ -498,7 +498,8 @@ class StyleTTSZS:
         rows form, fused into it (stzs_ln_linear, csrc/lnrows.hip: the normalised rows never leave the chip).
         t_lens (int32 [B] device tensor, ragged frames): utterance b holds t_lens[b] * t_lens_mul rows
         (stzs_conv_args.t_lens; the library refuses the forms that do not honour it); its fused statistics are
-        finalised here with the same lengths, never deferred."""
+        finalised here with the same lengths, never deferred.  t_lens_rows=1 (the ragged decoder): t_lens[b] is the
+        utterance's own row count on this conv's input time axis (stzs_conv_args.t_lens_rows)."""
         a, pro_ref = self._conv_fill(cw, x, y, what, T_out=T_out, pad=pad, dil=dil, stride=stride, pro=pro,
                                      pro_act=pro_act, pro_slope=pro_slope, pro_alpha=pro_alpha, cscale=cscale, res=res,
                                      res_tdiv=res_tdiv, acc_in=acc_in, alpha=alpha, beta=beta, gate=gate,
@@ -507,7 +508,7 @@ class StyleTTSZS:
         rows = self._conv_route(a, cw, x, y, flags, rows, cscale, res, stats_key)
         if t_lens is not None:
             assert collect is None and pro_ref is None and splitk <= 1 and rows == 0, what
-            a.t_lens, a.t_lens_mul = t_lens.data_ptr(), t_lens_mul
+            a.t_lens, a.t_lens_mul, a.t_lens_rows = t_lens.data_ptr(), t_lens_mul, t_lens_rows
         if rows > 1 or splitk > 1:
             self._conv_splitk(a, cw, x, splitk, rows, collect, what)
         if pro_ref is not None:
@@ -1662,13 +1663,65 @@ class StyleTTSZS:
                   collect=collect, what=key + ".conv2", **({} if flens is None else dict(t_lens=flens, t_lens_mul=fmul)))
 
     # ------------------------------------------------------------------ (c) decoder
-    def decode(self, pro: dict, codes: torch.Tensor, seeds, istft=True) -> torch.Tensor:
+    def decode(self, pro: dict, codes: torch.Tensor, seeds, istft=True, frame_lens=None, trace=None) -> torch.Tensor:
         """a9-a13: decoder pre-blocks, generator, conv_post + iSTFT.  pro: asr_buf (aligned text features in the
-        decoder input buffer), F0 / N [B, T80], T40 -> wav fp32 [B, 600 T40] (or conv_post rows, istft=False)."""
-        # the harmonic source depends on F0 only: forkable beside the decoder pre-blocks (fork site "src")
-        (gen_in, gbd), har = self.fork("src", lambda: self.decoder_pre(pro, codes),
-                                       lambda: self.sine_gen(pro["F0"], seeds))
-        return self.generator(gen_in, pro["F0"], seeds, gbd, istft=istft, har=har)
+        decoder input buffer), F0 / N [B, T80], T40 -> wav fp32 [B, 600 T40] (or conv_post rows, istft=False).
+        frame_lens (int32 [B] device tensor, the ragged decoder): row b holds frame_lens[b] of the T40
+        frames -- the alignment's totals, predict_prosody(ragged_frames=True)["frame_lens"] -- and is computed as
+        alone at T40 = frame_lens[b]: wav[b, :600 frame_lens[b]] are those bits, the tail exact zeros; no host sync.
+        trace (a dict): the stages' activations (generator())."""
+        if frame_lens is None:
+            # the harmonic source depends on F0 only: forkable beside the decoder pre-blocks (fork site "src")
+            (gen_in, gbd), har = self.fork("src", lambda: self.decoder_pre(pro, codes),
+                                           lambda: self.sine_gen(pro["F0"], seeds))
+            if trace is not None:
+                trace["gen_in"] = gen_in
+            return self.generator(gen_in, pro["F0"], seeds, gbd, trace=trace, istft=istft, har=har)
+        self._check_ragged_decoder()
+        rows = self.frame_rows(frame_lens, pro["T40"])  # (on the current stream, before the fork: both branches wait)
+        (gen_in, gbd), har = self.fork("src", lambda: self.decoder_pre(pro, codes, frame_lens),
+                                       lambda: self.sine_gen(pro["F0"], seeds, rows[0]))
+        if trace is not None:
+            trace["gen_in"] = gen_in
+        return self.generator(gen_in, pro["F0"], seeds, gbd, trace=trace, istft=istft, har=har, rows=rows)
+
+    def frame_rows(self, frame_lens: torch.Tensor, T40: int):
+        """the ragged decoder's row counts, from the rows' 40-fps frame counts (int32 [B] on the device, clamped into
+        [1, T40]) in ONE launch (stzs_frame_rows) -> int32 [B] device tensors: [0] the 80-fps rows 2 T_b (the decoder
+        output, the harmonic source's frames), [1 + i] the rows of generator stage i, 2 T_b prod r_j (+ 1 behind the
+        last stage's reflection pad: conv_post's rows and the iSTFT frame count)."""
+        S = self.spec
+        B = frame_lens.shape[0]
+        assert frame_lens.dtype == torch.int32 and frame_lens.shape == (B,) and frame_lens.is_contiguous()
+        n = 1 + len(S.up_rates)
+        out = self.buf("gen.frame_rows", (n, B), torch.int32)
+        a = L.FrameRowsArgs()
+        a.lens, a.out, a.B, a.T, a.n = frame_lens.data_ptr(), out.data_ptr(), B, int(T40), n
+        m = 2
+        a.mul[0] = m
+        for i, r in enumerate(S.up_rates):
+            m *= r
+            a.mul[1 + i], a.add[1 + i] = m, int(i == len(S.up_rates) - 1)
+        self._call(self.lib.stzs_frame_rows, a, "frame_rows")
+        return [out[k] for k in range(n)]
+
+    def _check_ragged_decoder(self):
+        """the ragged decoder runs where every generator conv takes a form with length-aware kernels
+        (stzs_conv_args.t_lens_rows = 1): the default bf16 engine -- not the latency engine's split-K blocks, not a
+        precise or fp32-decoder engine -- on a spec whose MRF convs and ConvTransposes are on the register-direct form
+        and whose conv_post is on the narrow form (SPEC_V0; not SPEC_TINY's generic convs).  Before any launch."""
+        self._check_ragged_frames()
+        if self.dec_dt != torch.bfloat16:
+            raise NotImplementedError("ragged decoder: the bf16 decoder only")
+        W = self.W
+        ok = all(getattr(lw[c], "frag32", False) and lw["k"] in (3, 7, 11)
+                 for st in W.rb for res in st for lw in res for c in ("c1", "c2"))
+        ok = ok and all(getattr(u, "frag32", False) and u.ci_pad // 128 <= 4 for u in W.ups)
+        ok = ok and getattr(W.conv_post, "narrow32", False)
+        if not ok:
+            raise NotImplementedError("ragged decoder: the generator's MRF convs and ConvTransposes must take the "
+                                      "register-direct form and conv_post the narrow form (generic-path convs do "
+                                      "not take per-row lengths)")
 
     def dec_style(self, codes: torch.Tensor) -> torch.Tensor:
         """every AdaIN gamma / beta of the decoder from the pooled acoustic codes: ONE GEMM -> [B, total] fp32."""
@@ -1680,9 +1733,13 @@ class StyleTTSZS:
         self.conv(ng.lin, Act(sa[:, None]), Act(gbd[:, None]), rows=self._rows_z(ng.lin), what="dec.norms")
         return gbd
 
-    def decoder_pre(self, pro: dict, codes: torch.Tensor):
+    def decoder_pre(self, pro: dict, codes: torch.Tensor, frame_lens=None):
         """a9: F0 / N stride-2 convs, asr_res, the encode block and the four decode blocks (1024 channels,
-        the last one x2 upsampling) -> (generator input [B, T80, dec_out], decoder AdaIN gammas/betas)."""
+        the last one x2 upsampling) -> (generator input [B, T80, dec_out], decoder AdaIN gammas/betas).
+        frame_lens (int32 [B] device tensor, ragged frames): the blocks take the rows' frame counts (blk(flens=...):
+        statistics, k3 convs, the upsampling); the F0 / N stride-2 convs need none -- output frame T_b - 1 reads F0 / N
+        rows 2 T_b - 3 .. 2 T_b - 1, inside the row -- and asr_res and the shortcuts are row-local.  Rows at and past
+        a row's end are finite and unspecified."""
         S, W = self.spec, self.W
         enc_in, F0, Nn, T40 = pro["asr_buf"], pro["F0"], pro["N"], pro["T40"]
         B = enc_in.B
@@ -1704,19 +1761,22 @@ class StyleTTSZS:
             self._call(self.lib.stzs_f0n_down, a, "f0n_down")
             self.conv(W.dec_asr_res, Act(enc_in.t, 0, S.d_txt), cat.sl(S.dec_enc, S.dec_asr_res), what="asr_res")
         self.blk(W.dec_blk["dec.encode"], Act(enc_in.t, 0, S.d_txt + 2), cats[0].sl(0, S.dec_enc), ng, gbd, "dec.encode",
-                 dt)
+                 dt, flens=frame_lens)
         src = 0
         for i in range(3):
             self.blk(W.dec_blk[f"dec.decode{i}"], Act(cats[src].t, 0, dcat), cats[1 - src].sl(0, S.dec_enc), ng, gbd,
-                     f"dec.decode{i}", dt)
+                     f"dec.decode{i}", dt, flens=frame_lens)
             src = 1 - src
         gen_in = self.act("dec.gen_in", B, T80, S.dec_out, dt)
-        self.blk(W.dec_blk["dec.decode3"], Act(cats[src].t, 0, dcat), gen_in, ng, gbd, "dec.decode3", dt)
+        self.blk(W.dec_blk["dec.decode3"], Act(cats[src].t, 0, dcat), gen_in, ng, gbd, "dec.decode3", dt,
+                 flens=frame_lens)
         return gen_in, gbd
 
-    def sine_gen(self, F0: torch.Tensor, seeds) -> Act:
+    def sine_gen(self, F0: torch.Tensor, seeds, lens=None) -> Act:
         """a10: NSF harmonic source from F0 [B, T80] (SineGen: fp64 frame-rate phase prefix, counter-RNG noise,
-        Linear(9->1) + tanh) and its n_fft-point STFT (real | imag) -> har [B, Tf, har_ch] (csrc/source.hip)."""
+        Linear(9->1) + tanh) and its n_fft-point STFT (real | imag) -> har [B, Tf, har_ch] (csrc/source.hip).
+        lens (int32 [B] device tensor, the ragged decoder): row b's 80-fps frames; its har rows past its own frame
+        count are zeros (stzs_source_args.lens)."""
         S, W = self.spec, self.W
         B, T80 = F0.shape[0], F0.shape[1]
         N = T80 * S.hop
@@ -1744,6 +1804,8 @@ class StyleTTSZS:
         a.B, a.T80, a.hop, a.n_fft, a.hop_s, a.nh = B, T80, S.hop, S.n_fft, S.istft_hop, nh
         a.sr, a.sine_amp, a.noise_std, a.voiced_thr = float(S.sr), S.sine_amp, S.noise_std, S.voiced_threshold
         a.har_dtype = har.dt
+        if lens is not None:
+            a.lens = lens.data_ptr()
         self._call(self.lib.stzs_harmonic_source, a, "harmonic_source",  # F0 in, prefix, STFT rows out
                    cost=(0, B * T80 * 4 * (1 + 2 * nh) + B * Tf * S.har_ch * har.t.element_size()))
         return har
@@ -1753,9 +1815,13 @@ class StyleTTSZS:
         s = math.prod(self.spec.up_rates[1:]) if len(self.spec.up_rates) > 1 else 1
         return _rup(Tf, s)
 
-    def upsample(self, x: Act, har: Act, i: int) -> Act:
+    def upsample(self, x: Act, har: Act, i: int, rows=None) -> Act:
         """a11: generator stage i's noise conv of the harmonic features + LeakyReLU(0.1) -> polyphase
-        ConvTranspose1d(k = 2 r, s = r) (+ ReflectionPad(1,0) on the last stage) + the noise conv as residual."""
+        ConvTranspose1d(k = 2 r, s = r) (+ ReflectionPad(1,0) on the last stage) + the noise conv as residual.
+        rows (int32 [B] device tensor, the ragged decoder): the rows of x each utterance holds -- the ConvTranspose
+        takes them (t_lens_rows 1); the noise convs take no length: they have no prologue and the harmonic-source rows
+        past an utterance's end are zeros, the padding they see at its end alone."""
+        rg = {} if rows is None else dict(t_lens=rows, t_lens_rows=1)
         S, W = self.spec, self.W
         B = x.B
         n_up = len(S.up_rates)
@@ -1772,7 +1838,7 @@ class StyleTTSZS:
             # column tile on the harmonic-source rows; its output never goes through HBM
             self.conv(nzw, x, xu, pro_act=L.ACT_LEAKY, pro_slope=0.1, ups_pad=(k - r) // 2, T_final=Tcur * r,
                       refl=1 if last else 0, res=Act(har.t, 0, har.ld), flags=L.CONV_UPS_NOISE,
-                      gate=self._t(nzw.nz32).data_ptr(), what=f"ups{i}")
+                      gate=self._t(nzw.nz32).data_ptr(), what=f"ups{i}", **rg)
             return xu
         xsrc = self.act(f"gen.xsrc{i}", B, Tn, c, dt)
         sup = W.noise_sup[i] if (not last and i < len(W.noise_sup)) else None
@@ -1793,19 +1859,22 @@ class StyleTTSZS:
         else:
             self.conv(W.noise_conv[i], har.sl(0, S.har_ch), xsrc, T_out=Tn, what=f"noise_conv{i}")
         self.conv(W.ups[i], x, xu, pro_act=L.ACT_LEAKY, pro_slope=0.1, ups_pad=(k - r) // 2, T_final=Tcur * r,
-                  refl=1 if last else 0, res=xsrc, what=f"ups{i}")
+                  refl=1 if last else 0, res=xsrc, what=f"ups{i}", **rg)
         return xu
 
-    def conv_post(self, x: Act) -> Act:
-        """LeakyReLU(0.01) + conv_post (128 -> 22, k7) -> fp32 rows [B, Tf, 22] (log-magnitude | phase argument)."""
+    def conv_post(self, x: Act, rows=None) -> Act:
+        """LeakyReLU(0.01) + conv_post (128 -> 22, k7) -> fp32 rows [B, Tf, 22] (log-magnitude | phase argument).
+        rows (int32 [B] device tensor, the ragged decoder): the rows of x each utterance holds."""
         S, W = self.spec, self.W
         post = self.act("gen.post", x.B, x.T, S.har_ch, torch.float32)
         self.conv(W.conv_post, x, Act(post.t, 0, S.har_ch), pad=3, pro_act=L.ACT_LEAKY, pro_slope=0.01,
-                  what="conv_post")
+                  what="conv_post", **({} if rows is None else dict(t_lens=rows, t_lens_rows=1)))
         return post
 
-    def istft(self, post: Act) -> torch.Tensor:
-        """a13: exp / sin spectrum, 20-point irfft, Hann overlap-add (hop 5), window-envelope normalisation."""
+    def istft(self, post: Act, lens=None) -> torch.Tensor:
+        """a13: exp / sin spectrum, 20-point irfft, Hann overlap-add (hop 5), window-envelope normalisation.
+        lens (int32 [B] device tensor, the ragged decoder): each utterance's frames; the samples past its own last one
+        are zeros (stzs_istft_args.lens)."""
         S = self.spec
         B, Tcur = post.B, post.T
         Nout = (Tcur - 1) * S.istft_hop
@@ -1813,31 +1882,35 @@ class StyleTTSZS:
         a = L.IstftArgs()
         a.post, a.wav, a.ldp, a.bsp, a.bsw = post.ptr, wav.data_ptr(), post.ld, post.bs, Nout
         a.B, a.Tf, a.n_fft, a.hop_s = B, Tcur, S.n_fft, S.istft_hop
+        if lens is not None:
+            a.lens = lens.data_ptr()
         self._call(self.lib.stzs_istft, a, "istft", cost=(0, B * Tcur * S.har_ch * 4 + B * Nout * 4))
         return wav
 
-    def generator(self, x: Act, F0: torch.Tensor, seeds, gbd, trace=None, istft=True, har: Act = None):
+    def generator(self, x: Act, F0: torch.Tensor, seeds, gbd, trace=None, istft=True, har: Act = None, rows=None):
         """a10-a13: harmonic source, per stage the noise conv + ConvTranspose up-sampling and the MRF, then
-        conv_post and the iSTFT.  har: precomputed harmonic-source features (the chunked decoder's window slice)."""
+        conv_post and the iSTFT.  har: precomputed harmonic-source features (the chunked decoder's window slice).
+        rows (frame_rows(), the ragged decoder): the row counts of x ([0]) and of every stage's output ([1 + i])."""
         S, W = self.spec, self.W
         ng = W.dec_norm
+        rw = (lambda k: None) if rows is None else (lambda k: rows[k])
         if har is None:
-            har = self.sine_gen(F0, seeds)
+            har = self.sine_gen(F0, seeds, rw(0))
         if trace is not None:
             trace["har"] = har
         for i in range(len(S.up_rates)):
-            xu = self.upsample(x, har, i)
+            xu = self.upsample(x, har, i, rw(i))
             if trace is not None:
                 trace[f"mrf_in{i}"] = xu
-            x = self.mrf(xu, i, gbd, ng)
+            x = self.mrf(xu, i, gbd, ng, rw(1 + i))
             if trace is not None:
                 trace[f"mrf_out{i}"] = x
-        post = self.conv_post(x)
+        post = self.conv_post(x, rw(len(S.up_rates)))
         if trace is not None:
             trace["post"] = post
         if not istft:
             return post
-        return self.istft(post)
+        return self.istft(post, rw(len(S.up_rates)))
 
     def _istft_chunk(self, rows_ptr, ldp, bsp, B, f0, Fc, fin, wav, tails, i):
         """one streaming-iSTFT launch: conv_post frames [f0, f0 + Fc) at rows_ptr (row pitch ldp, batch stride bsp,
@@ -1990,14 +2063,14 @@ class StyleTTSZS:
         for r in refs:
             r.done = True
 
-    def _rb_c1(self, lw, x: Act, y: Act, st, gbd, ng, stats_key, collect=None):
+    def _rb_c1(self, lw, x: Act, y: Act, st, gbd, ng, stats_key, collect=None, **kw):
         """a resblock layer's first conv (dilated) over Snake(AdaIN(x)), st = x's (mean, rstd, stat_bs), with y's
         statistics fused -> (mean, rstd, stat_bs) of y"""
         k, dil = lw["k"], lw["dil"]
         o1, c1 = ng.offsets[lw["n1"]]
         return self.conv(lw["c1"], x, y, pad=dil * (k - 1) // 2, dil=dil,
                          pro=(*st, gbd.data_ptr() + o1 * 4, ng.total, c1), pro_act=L.ACT_SNAKE, pro_alpha=lw["a1"],
-                         stats_key=stats_key, collect=collect, what="rb.c1")[1]
+                         stats_key=stats_key, collect=collect, what="rb.c1", **kw)[1]
 
     def _rb_c2(self, lw, x: Act, y: Act, st, res: Act, gbd, ng, **kw):
         """a resblock layer's second conv over Snake(AdaIN(x)) + res; kw: the caller's epilogue / statistics /
@@ -2049,9 +2122,14 @@ class StyleTTSZS:
         return (self.mrf_trio and self.timer is None and x.B <= 4 and tuple(self.spec.rb_kernels) == (3, 7, 11) and
                 len({len(res) for res in rb}) == 1 and all(r["k"] == k for res, k in zip(rb, (3, 7, 11)) for r in res))
 
-    def mrf(self, x: Act, i, gbd, ng):
+    def mrf(self, x: Act, i, gbd, ng, rows=None):
+        """a12: the stage's resblocks (k 3 / 7 / 11) summed / 3.  rows (int32 [B] device tensor, the ragged decoder):
+        the rows of x each utterance holds -- the statistics and every Snake conv take them (t_lens_rows 1), each
+        conv's fused statistics finalised where they are produced with the same array (no deferral, no trio): the
+        uniform path's bits row for row."""
         S, W = self.spec, self.W
-        if self._mrf_trio_on(x, i):
+        rg = {} if rows is None else dict(t_lens=rows, t_lens_rows=1)
+        if rows is None and self._mrf_trio_on(x, i):
             return self._mrf_trio(x, i, gbd, ng)
         B, T, c = x.B, x.T, x.C
         dt = x.t.dtype
@@ -2059,17 +2137,17 @@ class StyleTTSZS:
         bufA = self.act(f"gen.ba{i}", B, T, c, dt)
         bufB = self.act(f"gen.bb{i}", B, T, c, dt)
         t1 = self.act(f"gen.t1_{i}", B, T, c, dt)
-        mx, rx, sb = self.stats(x, f"gen.sx{i}")
+        mx, rx, sb = self.stats(x, f"gen.sx{i}", rows)
         nk = len(S.rb_kernels)
         for j, res in enumerate(W.rb[i]):
             cur, cm, cr = x, mx, rx
             for m, lw in enumerate(res):
-                tm, tr, _ = self._rb_c1(lw, cur, t1, (cm, cr, sb), gbd, ng, f"gen.st{i}")
+                tm, tr, _ = self._rb_c1(lw, cur, t1, (cm, cr, sb), gbd, ng, f"gen.st{i}", **rg)
                 last = m == len(res) - 1
                 out = xs if last else (bufA if cur is not bufA else bufB)
                 r2 = self._rb_c2(lw, t1, out, (tm, tr, sb), cur, gbd, ng, alpha=(1.0 / nk) if last else 1.0,
                                  acc_in=(xs if (last and j > 0) else None), beta=1.0,
-                                 stats_key=None if last else f"gen.sc{i}.{m % 2}")
+                                 stats_key=None if last else f"gen.sc{i}.{m % 2}", **rg)
                 if not last:
                     _, (cm, cr, _) = r2
                     cur = out
@@ -2123,13 +2201,17 @@ class StyleTTSZS:
         return torch.cuda.is_current_stream_capturing()
 
     def synth(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None, codes=None,
-              n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None):
+              n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None, ragged_frames=False):
         """tokens int [B, T_txt]; ref_wav fp32 [B|1, N]; noise fp32 [B, L_s, code]; durations int [B, T_txt]
         (host tensor, or device tensor + n_frames: no device sync); seeds: per-utterance source-noise
         seeds; prompt_idx: teacher-forced discrete prompt codes [B|1, L_s, G] (ref_wav then unused).
         text_lens: int [B] (host: range-checked; int32 device tensor: trusted, no sync), each in [1, T_txt] -- a
         ragged batch: row b is computed as alone on its first text_lens[b] tokens (DESIGN.md "Ragged text
-        batches").  The decoder is not ragged: the rows must still share one frame count.
+        batches").  Without ragged_frames the rows must still share one frame count.
+        ragged_frames=True: the rows need not share their frame count -- ragged prosody
+        (predict_prosody(ragged_frames=True)) and the ragged decoder (decode(frame_lens=...)) at the padded width of
+        the longest row (or n_frames) -> (wav [B, 600 T40], frame_lens int32 [B] on the device): row b is valid to
+        600 frame_lens[b], the bits of the row alone, and exact zeros from there.
         ref_lens: int [B|1], one per row of ref_wav (host: range-checked; int32 device tensor: trusted, no sync), each
         in [mel_nfft / 2 + 1, N] -- a ragged reference batch: row b's prompt is computed as alone on
         ref_wav[b, :ref_lens[b]], what lies past it is never read; ignored, as ref_wav is, when
@@ -2138,15 +2220,19 @@ class StyleTTSZS:
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
         -> dict(wav=[B, 600*T40], prompt_idx=[B|1, L_s, G], status=int32 [1], ...)"""
+        if ragged_frames:
+            self._check_ragged_decoder()
         h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                                   n_frames, prompt_idx, text_lens, ref_lens)
-        wav = self.decode(pro, codes, seeds)
+                                                   n_frames, prompt_idx, text_lens, ref_lens, ragged_frames)
+        wav = self.decode(pro, codes, seeds, frame_lens=pro["frame_lens"] if ragged_frames else None)
         if check and not self._capturing():
             self.check_status()
+        if ragged_frames:
+            return wav, pro["frame_lens"]
         return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
 
     def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx,
-               text_lens=None, ref_lens=None):
+               text_lens=None, ref_lens=None, ragged_frames=False):
         """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
         encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
         -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
@@ -2162,7 +2248,7 @@ class StyleTTSZS:
             prompt = pe
         if codes is None:
             codes = self.sample_style(h, prompt, noise.to(dev, torch.float32), steps, cfg_scale, text_lens)
-        pro = self.predict_prosody(h, codes, durations, n_frames, text_lens)
+        pro = self.predict_prosody(h, codes, durations, n_frames, text_lens, ragged_frames)
         return h, prompt, codes, pro, list(range(B)) if seeds is None else seeds
 
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,

@@ -35,6 +35,12 @@ batch per chunk at the padded width of its longest row (the engine's ragged_fram
 own T_b frames); phase 2b groups by T40 as before, cuts each bucket's rows out of the prosody results
 (engine.prosody_rows: data movement only) and runs the decoder per bucket.  With it off the schedule is, call for
 call, the present one.
+
+ragged_decoder=True (off by default; requires ragged_frames) keeps phase 2 in one piece again, now on ragged batches:
+the requests are sorted by their frame count (known on the host after phase 1; neighbours in the order share the least
+padding) and cut into chunks of <= max_batch; each chunk runs ONE ragged prosody batch and ONE ragged decoder pass on
+its result (the engine's decode(frame_lens=...): row b is computed as alone on its own T_b frames) --
+no per-row copies -- and request i's waveform is the first 600 T40_i samples of its row.
 """
 from __future__ import annotations
 
@@ -59,11 +65,17 @@ class Request:
 
 class BucketScheduler:
     def __init__(self, engine: StyleTTSZS, max_batch: int = 64, steps: int = 2, cfg_scale: float = 5.0,
-                 ragged_text: bool = False, ragged_ref: bool = False, ragged_frames: bool = False):
+                 ragged_text: bool = False, ragged_ref: bool = False, ragged_frames: bool = False,
+                 ragged_decoder: bool = False):
+        if ragged_decoder and not ragged_frames:
+            raise ValueError("ragged_decoder requires ragged_frames (the ragged decoder reads the ragged prosody's rows)")
         if ragged_frames:
             engine._check_ragged_frames()  # (NotImplementedError on the latency / precise engines, before any launch)
+        if ragged_decoder:
+            engine._check_ragged_decoder()  # (... and on a spec whose generator convs do not take the lengths)
         self.eng, self.max_batch, self.steps, self.cfg = engine, max_batch, steps, cfg_scale
         self.ragged_text, self.ragged_ref, self.ragged_frames = ragged_text, ragged_ref, bool(ragged_frames)
+        self.ragged_decoder = bool(ragged_decoder)
         self.stats = {}
 
     def _chunks(self, ids):
@@ -89,7 +101,11 @@ class BucketScheduler:
         """the phase-2 batches for the requests' frame counts, in launch order -> (prosody batches, decoder batches),
         each a list of request-index lists of at most max_batch.  Without ragged_frames a batch shares its T40 and
         runs prosody and decoder together (the two lists are the same); with it the prosody batches are chunks of the
-        requests in request order and only the decoder batches share a T40.  Pure host bookkeeping."""
+        requests in request order and only the decoder batches share a T40; with ragged_decoder as well, both lists
+        are the chunks of the requests sorted by T40 (a stable sort).  Pure host bookkeeping."""
+        if self.ragged_decoder:
+            ch = list(self._chunks(sorted(range(len(frames)), key=lambda i: int(frames[i]))))
+            return ch, ch
         g2 = OrderedDict()
         for i, n in enumerate(frames):
             g2.setdefault(int(n), []).append(i)
@@ -137,6 +153,24 @@ class BucketScheduler:
             for j, i in enumerate(ch):
                 out[i] = wav[j].clone()
         return len(pros), len(dec), fr_n, pad_n
+
+    def _phase2_ragged_decoder(self, per, out):
+        """phase 2 with the ragged decoder: per chunk of requests (sorted by frame count) one ragged prosody batch and
+        one ragged decoder pass on it -> (batches, padded frame blocks, of them tail)"""
+        eng, S = self.eng, self.eng.spec
+        chunks, _ = self.phase2_groups([p["T40"] for p in per])
+        fr_n = pad_n = 0
+        for ch in chunks:
+            h, d, dur, codes = self._phase2_inputs(per, ch)
+            Tp = max(per[i]["T40"] for i in ch)
+            pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, Tp, ragged_frames=True)
+            wav = eng.decode(pro, codes, [per[i]["seed"] for i in ch], frame_lens=pro["frame_lens"])
+            fr_n += Tp * len(ch)
+            pad_n += Tp * len(ch) - sum(per[i]["T40"] for i in ch)
+            n = S.frame40  # samples per 40-fps frame
+            for j, i in enumerate(ch):
+                out[i] = wav[j, :n * per[i]["T40"]].clone()
+        return len(chunks), fr_n, pad_n
 
     def synth(self, reqs: List[Request]) -> List[torch.Tensor]:
         """-> one fp32 waveform [600 * T40_i] per request, in request order (device tensors)."""
@@ -199,7 +233,10 @@ class BucketScheduler:
         out = [None] * len(reqs)
         n2 = 0
         npro, fr_n, fpad_n = None, 0, 0
-        if self.ragged_frames:
+        if self.ragged_decoder:
+            n2, fr_n, fpad_n = self._phase2_ragged_decoder(per, out)
+            npro = n2
+        elif self.ragged_frames:
             npro, n2, fr_n, fpad_n = self._phase2_ragged(per, out)
         for T40, ids in ([] if self.ragged_frames else g2.items()):
             for ch in self._chunks(ids):
@@ -223,5 +260,8 @@ class BucketScheduler:
                           ref_pad_share=pad_n / max(ref_n, 1),
                           # prosody batches (ragged_frames: fewer than the decoder's; else one per phase-2 batch) and
                           # the share of the padded prosody frame blocks that is tail
-                          prosody_batches=n2 if npro is None else npro, frame_pad_share=fpad_n / max(fr_n, 1))
+                          prosody_batches=n2 if npro is None else npro, frame_pad_share=fpad_n / max(fr_n, 1),
+                          # decoder passes, and the share of their padded frame blocks that is tail (ragged_decoder:
+                          # the prosody's; else a decoder batch shares its frame count)
+                          decoder_batches=n2, decoder_pad_share=fpad_n / max(fr_n, 1) if self.ragged_decoder else 0.0)
         return out

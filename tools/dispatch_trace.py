@@ -429,6 +429,50 @@ def sweep_calls():
                                       ({}, dict(pro_part=PTR["pro_part"], pro_nch=2, pro_T=100, pro_ld=256))]),
                ("pair.pro_part both", [conv(B=1, Ci=256, ks=3, cic=64, splitk=4, adain=True, pro_part=PTR["pro_part"], pro_nch=2,
                                             pro_T=100, pro_ld=256) for _ in range(2)])]
+    # the ragged decoder (t_lens_rows = 1: an utterance's own row count): the register-direct Snake convs, the
+    # polyphase ConvTranspose and the narrow conv_post form launch instances of their own ("trows ..."); every other form
+    # or combination is refused before any runtime call ("trows.bad ...": STZS_EINVAL, nothing launched)
+    TR = dict(t_lens=TL, t_lens_rows=1)
+    epi = (("plain", {}), ("res.stat", dict(res=True, stat=True)), ("res.alpha", dict(res=True, alpha=1 / 3)),
+           ("res.acc.alpha", dict(res=True, acc=True, alpha=1 / 3)), ("res.acc", dict(res=True, acc=True)))
+    for Ci, ks, (elab, ekw), (B, T) in itertools.product((128, 256), (3, 7, 11), epi, ((4, 200), (64, 1030))):
+        for fl in ((0, MRFV_NARROW) if (Ci == 256 and B == 64) else (0,)):
+            one(f"trows frag32.snake Ci{Ci} ks{ks} {elab} B{B} f{fl}",
+                conv(B=B, T=T, Ci=Ci, Co=256, ks=ks, dil=5 if ks == 11 else 1, cic=128, flags=FRAG32 | fl, pro_act=SNAKE,
+                     adain=True, **ekw, **TR))
+    for Ci, r, nz, refl, (B, T) in itertools.product((128, 256, 384, 512), (0, 1), (0, 1), (0, 1), ((4, 40), (64, 130))):
+        kw = dict(gate=True, res=True, ldr=32, bsr=32 * 1000) if nz else dict(res=bool(r))
+        one(f"trows frag32.ups Ci{Ci} r{r} nz{nz} refl{refl} B{B}",
+            conv(B=B, T=T, Ci=Ci, Co=128, ups=4, cic=128, flags=FRAG32 | (UPS_NOISE if nz else 0), pro_act=LEAKY, refl=refl,
+                 **kw, **TR))
+    n7 = conv(B=4, T=200, Ci=128, Co=22, ks=7, cic=128, flags=NARROW32, outd=F32, pro_act=LEAKY, ldy=24, **TR)
+    one("trows narrow32", n7)
+    one("trows narrow32 mul1", dict(n7, t_lens_mul=1))
+    s3 = conv(B=4, T=200, Ci=256, Co=256, ks=3, cic=128, flags=FRAG32, pro_act=SNAKE, adain=True, **TR)
+    for lab, d in (("mfma snake", conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, adain=True, pro_act=SNAKE, **TR)),
+                   ("mfma leaky", conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, adain=True, pro_act=LEAKY, **TR)),
+                   ("lane16", conv(Ci=256, ks=3, cic=128, flags=LANE16, pro_act=SNAKE, **TR)),
+                   ("x3frag", conv(Ci=256, ks=3, cic=128, flags=FRAG32X3, ind=F32, outd=F32, pro_act=SNAKE, **TR)),
+                   ("x3", conv(Ci=64, ks=3, flags=X3, ind=F32, outd=F32, **TR)),
+                   ("rows", conv(B=1, T=20, Ci=512, Co=200, flags=ROWS, **TR)),
+                   ("glds", conv(Ci=256, flags=A_DMA, **TR)),
+                   ("splitk", dict(s3, B=1, splitk=2, splitk_ws=PTR["splitk_ws"], splitk_ctr=PTR["splitk_ctr"])),
+                   ("mul 2", dict(s3, t_lens_mul=2)), ("mul -1", dict(s3, t_lens_mul=-1)), ("rows 2", dict(s3, t_lens_rows=2)),
+                   ("rows -1", dict(s3, t_lens_rows=-1)), ("rows 1 no lengths", dict(s3, t_lens=0)), ("lengths+2", dict(s3, t_lens=TL + 2)),
+                   ("stride 2", dict(s3, stride=2, T_out=100)), ("T_out-1", dict(s3, T_out=199)),
+                   ("pro_part", dict(s3, pro_part=PTR["pro_part"], pro_nch=2, pro_T=200, pro_ld=256)),
+                   ("frag32 blk leaky", dict(s3, pro_act=LEAKY)), ("frag32 blk none", dict(s3, pro_act=NONE)),
+                   ("frag32 ks 1 shortcut", conv(B=4, T=200, Ci=256, Co=256, cic=128, flags=FRAG32, **TR)),
+                   ("frag32 acc no res", dict(s3, acc_in=PTR["acc_in"], lda=256, bsa=200 * 256)),
+                   ("frag32 alpha no res", dict(s3, alpha=0.5)),
+                   ("frag32 ups mul 2", conv(Ci=256, Co=128, ups=4, cic=128, flags=FRAG32, pro_act=LEAKY, t_lens=TL, t_lens_rows=1, t_lens_mul=2)),
+                   ("frag32 ups rows 2", conv(Ci=256, Co=128, ups=4, cic=128, flags=FRAG32, pro_act=LEAKY, t_lens=TL, t_lens_rows=2)),
+                   ("mfma ups", conv(Ci=256, Co=64, ups=4, cic=64, pro_act=LEAKY, **TR)),
+                   ("narrow32 rows 2", dict(n7, t_lens_rows=2)), ("narrow32 mul 2", dict(n7, t_lens_mul=2))):
+        one(f"trows.bad {lab}", d)
+    # (groups with lengths run one stzs_conv1d at a time: the trio and pair launches stay length-free)
+    groups += [("trows trio", trio(Ci=256, adain=True, **TR)), ("trows.bad trio", trio(adain=True, t_lens=TL, t_lens_rows=2)),
+               ("trows.bad trio mul 2", trio(adain=True, t_lens_mul=2, **TR))]
     for lab, ds in groups:
         calls.append((f"group {lab}", "stzs_conv1d_group", ds, None))
     for lab, ds in (groups[0], groups[2], groups[12]):  # a defect in one member of a group

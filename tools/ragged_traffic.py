@@ -4,16 +4,17 @@ batches" and §2c "Ragged reference batches").
 64 requests on SPEC_V0: token counts drawn with a fixed seed from 20..200, 3-s references (--ref-s LO,HI: reference
 lengths drawn with the same seed, uniformly in samples, from LO..HI seconds), 2 steps, CFG 5, predicted durations.
 One engine, the same requests; the schedules -- plain (neither flag: the baseline), ragged (ragged_text=True),
-ragged_ref (ragged_text=True and ragged_ref=True) and ragged_frames (all three flags: prosody in one ragged batch per
-max_batch requests) -- are timed in alternation after a warm-up of each -- a host clock
+ragged_ref (ragged_text=True and ragged_ref=True), ragged_frames (those and ragged_frames: prosody in one ragged batch
+per max_batch requests) and ragged_decoder (all four flags: the decoder too runs one ragged pass per
+max_batch requests, sorted by frame count) -- are timed in alternation after a warm-up of each -- a host clock
 around synth() ending in a device synchronise -- and the medians, the phase-1 batch counts, the phase-1 wall time
 (each phase-1 batch ends in a host sync, so the scheduler's own clock is the phase's) and the share of the phase-1
 reference blocks that is padding go out as one JSON line.
 
     python tools/ragged_traffic.py [--requests 64] [--runs 7] [--warmup 2] [--ref-s LO,HI]
-                                   [--mode both|all|plain|ragged|ragged_ref|ragged_frames]
+                                   [--mode both|all|plain|ragged|ragged_ref|ragged_frames|ragged_decoder]
 
---mode both: plain and ragged (the measurement of "Ragged text batches"); all: the four schedules.
+--mode both: plain and ragged (the measurement of "Ragged text batches"); all: the five schedules.
 """
 import argparse
 import json
@@ -50,7 +51,8 @@ def main():
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--max-batch", type=int, default=64)
-    ap.add_argument("--mode", choices=("both", "all", "plain", "ragged", "ragged_ref", "ragged_frames"), default="both")
+    ap.add_argument("--mode", choices=("both", "all", "plain", "ragged", "ragged_ref", "ragged_frames", "ragged_decoder"),
+                    default="both")
     ap.add_argument("--ref-s", default=None, metavar="LO,HI",
                     help="reference lengths seeded uniformly in [LO, HI] seconds (default: 3 s for every request)")
     a = ap.parse_args()
@@ -67,16 +69,17 @@ def main():
         raise SystemExit("ragged_traffic.py measures on the GPU: none is visible")
     eng = StyleTTSZS(S, init_params(S, seed=0), device="cuda:0")
     reqs = make_requests(S, a.requests, ref_s=ref_s)
-    # (ragged_text, ragged_ref, ragged_frames)
-    modes = {"plain": (False, False, False), "ragged": (True, False, False), "ragged_ref": (True, True, False),
-             "ragged_frames": (True, True, True)}
+    # (ragged_text, ragged_ref, ragged_frames, ragged_decoder)
+    modes = {"plain": (False, False, False, False), "ragged": (True, False, False, False),
+             "ragged_ref": (True, True, False, False), "ragged_frames": (True, True, True, False),
+             "ragged_decoder": (True, True, True, True)}
     if a.mode == "both":
         modes = {m: modes[m] for m in ("plain", "ragged")}
     elif a.mode != "all":
         modes = {a.mode: modes[a.mode]}
     sch = {m: BucketScheduler(eng, max_batch=a.max_batch, steps=STEPS, cfg_scale=CFG, ragged_text=rt, ragged_ref=rr,
-                              ragged_frames=rf)
-           for m, (rt, rr, rf) in modes.items()}
+                              ragged_frames=rf, ragged_decoder=rd)
+           for m, (rt, rr, rf, rd) in modes.items()}
     wall = {m: [] for m in sch}
     ph1 = {m: [] for m in sch}
     outs = {}
@@ -107,7 +110,8 @@ def main():
                       wall_ms_max=round(max(wall[m]), 2), phase1_ms_median=round(statistics.median(ph1[m]), 2),
                       phase1_ms_min=round(min(ph1[m]), 2), phase1_ms_max=round(max(ph1[m]), 2),
                       ref_pad_share=round(st["ref_pad_share"], 4), prosody_batches=st["prosody_batches"],
-                      frame_pad_share=round(st["frame_pad_share"], 4))
+                      frame_pad_share=round(st["frame_pad_share"], 4), decoder_batches=st["decoder_batches"],
+                      decoder_pad_share=round(st["decoder_pad_share"], 4))
     if "plain" in sch:  # every schedule computed the same waveforms
         for m in sch:
             if m != "plain":
