@@ -547,11 +547,11 @@ int stzs_harmonic_source(const stzs_source_args* a, void* stream);
  * hop_s == n_fft is refused (STZS_ESHAPE): the periodic Hann window's first tap is 0, so the samples f * n_fft would
  * have a zero envelope (torch.istft refuses it too).  The phase argument p is reduced with a two-constant 2 pi that is
  * exact for |p| < 2^17.
- * lens (optional, NULL = the call as before; the ragged decoder; stzs_istft only, the streaming entry points are not
- * ragged): int32 [B] on the device, the frames Tf_b of utterance b, clamped into [2, Tf]: its last frame, the padded
- * sample bound and the window-square envelope are those of Tf_b -- wav[b, n < (Tf_b - 1) * hop_s] are the bits of the
- * utterance alone at Tf = Tf_b, the samples from there to (Tf - 1) * hop_s are stored as exact zeros, post rows
- * >= Tf_b are not read. */
+ * lens (optional, NULL = the call as before; the ragged decoder; the streaming entry point takes per-utterance
+ * counts too, see stzs_istft_stream_args): int32 [B] on the device, the frames Tf_b of utterance b, clamped into
+ * [2, Tf]: its last frame, the padded sample bound and the window-square envelope are those of Tf_b --
+ * wav[b, n < (Tf_b - 1) * hop_s] are the bits of the utterance alone at Tf = Tf_b, the samples from there to
+ * (Tf - 1) * hop_s are stored as exact zeros, post rows >= Tf_b are not read. */
 typedef struct stzs_istft_args {
     const float* post;
     float* wav;
@@ -568,7 +568,20 @@ int stzs_istft(const stzs_istft_args* a, void* stream);
  * tail_out receives frames f0+Fc-halo .. f0+Fc-1 (must not alias tail_in: ping-pong two buffers).
  * The chunk writes samples n in [n0, n1) (stzs_istft_stream_span) to wav[b*bsw + n - n0]; the
  * final chunk also emits the trailing samples up to (f0 + Fc - 1) * hop_s.  Concatenated chunks
- * are bit-identical to stzs_istft over the whole utterance (same kernel, same summation order). */
+ * are bit-identical to stzs_istft over the whole utterance (same kernel, same summation order).
+ * lens (optional, NULL = the launch as before, same kernel instance, every bit; ragged streaming): int32 [B] on the
+ * device, the ABSOLUTE frame count Tf_b of utterance b, taken as max(lens[b], 2) -- no upper clamp, the call does not
+ * know the total: the caller passes counts <= the batch's last frame + 1.  f0, Fc, final_chunk and the span keep their
+ * batch-wide meaning (the longest utterance).  With E_b = (Tf_b - 1) * hop_s, every sample n < E_b of the span is the
+ * bit pattern stzs_istft gives utterance b alone at Tf = Tf_b (its last frame, padded-sample bound and envelope are
+ * those of Tf_b), every sample n >= E_b an exact zero.  An utterance is finalised by its own count, in whatever chunk
+ * its last samples fall into -- also one that holds none of its frames (its last frame was the previous chunk's last:
+ * the remaining n_fft / 2 - hop_s samples come from tail_in alone).  Frames f >= Tf_b are never read from post and
+ * their tail_out rows are stored as zeros.
+ * post_off (optional, NULL = 0 everywhere; a negative entry is taken as 0): int32 [B] on the device, frame f0 + j of
+ * utterance b is read at post + b * bsp + (post_off[b] + j) * ldp -- one launch reads each utterance's chunk frames
+ * from a place of its own (the ragged chunked decoder's windows).
+ * lens / post_off not 4-byte aligned: STZS_EINVAL, before any launch. */
 typedef struct stzs_istft_stream_args {
     const float* post;     /* chunk frames: row j = frame f0 + j, [B, Fc, ldp] */
     const float* tail_in;
@@ -576,6 +589,8 @@ typedef struct stzs_istft_stream_args {
     float* wav;
     int64_t ldp, bsp, bsw, ldt;
     int32_t B, f0, Fc, final_chunk, n_fft, hop_s;
+    const int32_t* lens;
+    const int32_t* post_off;
 } stzs_istft_stream_args;
 int stzs_istft_stream(const stzs_istft_stream_args* a, void* stream);
 /* -> halo (>= 0) or a negative error; [*n0, *n1) = output samples of the chunk.  Host arithmetic only: any even

@@ -11,6 +11,14 @@
 // order with the same frame synthesis code in both modes, so concatenated chunks are BIT-identical
 // to the whole-utterance output (tests/test_gpu_stream.py).
 //
+// A ragged batch (lens: per-utterance frame counts, in both calls): utterance b's last frame, padded-sample bound and
+// envelope are those of its own count Tf_b, so its samples below (Tf_b - 1) hop are the bits of the utterance alone and
+// the rest of the span is stored as zeros.  In the streaming call the counts are absolute and an utterance is
+// finalised by its own count in whatever chunk its last samples fall into -- also one that holds none of its frames
+// (its last frame was the previous chunk's last: the remaining n_fft / 2 - hop samples come from the carried tail
+// alone).  Frames at or past Tf_b are never read and are carried as zero tail rows; a workgroup whose whole span lies
+// past the utterance's end stores zeros and skips the synthesis (tests/test_gpu_ragged_stream_kernels.py).
+//
 // Work split: one workgroup per 256 - halo frames of the chunk, so the 256 frame signals overlapping its output span
 // (its own + the halo) are synthesised once into LDS by the 256 threads in ONE pass (256 own frames + 3 halo took a
 // second pass for 3 threads, i.e. the whole workgroup twice as long), then each thread overlap-adds its output
@@ -31,9 +39,12 @@ struct IstftJob {
     float* wav;            // wav[b * bsw + n - n0]
     long ldp, bsp, bsw, ldt, n0, m_end;  // m_end: exclusive padded-sample bound of the chunk
     int B, f0, Fc, hs;
-    // a ragged batch (stzs_istft only: the whole utterance, f0 = 0, final): frames per utterance, clamped into [2, Fc];
-    // utterance b's last frame and sample bound are those of its own count, the samples up to m_end stored as zeros
+    // a ragged batch: ABSOLUTE frames per utterance, taken as max(lens[b], 2); utterance b's last frame and sample
+    // bound are the smaller of the chunk's and those of its own count, the samples from there to m_end stored as zeros
+    // (the whole utterance is the chunk [0, Tf): its count is thereby clamped into [2, Tf])
     const int32_t* lens;
+    // streaming only: utterance b's chunk frames start post_off[b] rows into post (negative = 0)
+    const int32_t* post_off;
 };
 
 STZS_DEV int halo_of(int nfft, int hs) { return (nfft + hs - 1) / hs - 1; }
@@ -53,10 +64,13 @@ __global__ __launch_bounds__(256) void istft_kernel(const IstftJob a) {
     const int fb0 = a.f0 + blockIdx.x * FB;  // absolute first frame of this block
     int flast = a.f0 + a.Fc - 1;             // last frame of the chunk
     long m_end = a.m_end;
-    if (a.lens) {  // (uniform per workgroup; f0 = 0)
+    int fown = 0x7fffffff;  // the utterance's own last frame (a ragged batch)
+    if (a.lens) {           // (uniform per workgroup)
         const int v = a.lens[b];
-        flast = (v < 2 ? 2 : (v > a.Fc ? a.Fc : v)) - 1;
-        m_end = (long)flast * hs + nfft / 2;
+        fown = (v < 2 ? 2 : v) - 1;
+        if (fown < flast) flast = fown;
+        const long m_own = (long)fown * hs + nfft / 2;
+        if (m_own < m_end) m_end = m_own;
     }
     if (tid < nfft) {
         const double ang = 2.0 * 3.141592653589793 * tid / nfft;
@@ -65,18 +79,36 @@ __global__ __launch_bounds__(256) void istft_kernel(const IstftJob a) {
         win[tid] = (float)(0.5 - 0.5 * cos(ang));
     }
     const float* Pp = a.post + (long)b * a.bsp;
+    if (a.post_off) {
+        const int po = a.post_off[b];
+        if (po > 0) Pp += (long)po * a.ldp;
+    }
     const float* Tp = a.tail_in ? a.tail_in + (long)b * halo * a.ldt : nullptr;
-    // carried tail for the next chunk: raw rows of the chunk's last `halo` frames (block 0 writes it)
+    // carried tail for the next chunk: raw rows of the chunk's last `halo` frames (block 0 writes it); a ragged batch
+    // carries zeros for the frames past the utterance's own last one and never reads them
     if (a.tail_out && blockIdx.x == 0) {
         float* To = a.tail_out + (long)b * halo * a.ldt;
         for (int e = tid; e < halo * (nfft + 2); e += 256) {
             const int i = e / (nfft + 2), c = e - i * (nfft + 2);
             const int f = a.f0 + a.Fc - halo + i;
             float v = 0.f;
-            if (f >= a.f0) v = Pp[(long)(f - a.f0) * a.ldp + c];
+            if (f > fown) v = 0.f;
+            else if (f >= a.f0) v = Pp[(long)(f - a.f0) * a.ldp + c];
             else if (f >= 0 && Tp) v = Tp[(long)(a.Fc + i) * a.ldt + c];
             To[(long)i * a.ldt + c] = v;
         }
+    }
+    if (a.lens && (long)fb0 * hs >= m_end) {
+        // a ragged batch: the whole output span of this workgroup lies at or past the utterance's own end -- zeros, no
+        // frame synthesis (the branch is uniform for the workgroup: b and blockIdx.x alone decide it, no barrier follows)
+        float* Wz = a.wav + (long)b * a.bsw;
+        for (int s = tid; s < FB * hs; s += 256) {
+            const long m = (long)fb0 * hs + s;
+            const long n = m - nfft / 2;
+            if (n < a.n0 || m >= a.m_end) continue;
+            Wz[n - a.n0] = 0.f;
+        }
+        return;
     }
     __syncthreads();
     for (int q = tid; q < NF; q += 256) {
@@ -84,7 +116,7 @@ __global__ __launch_bounds__(256) void istft_kernel(const IstftJob a) {
         float* o = fr + q * nfft;
         const float* row = nullptr;
         if (f >= a.f0 && f <= flast) row = Pp + (long)(f - a.f0) * a.ldp;
-        else if (f >= 0 && f < a.f0 && Tp) row = Tp + (long)(f - (a.f0 - halo)) * a.ldt;
+        else if (f >= 0 && f < a.f0 && f <= flast && Tp) row = Tp + (long)(f - (a.f0 - halo)) * a.ldt;
         if (!row) {
             for (int i = 0; i < nfft; ++i) o[i] = 0.f;
             continue;
@@ -207,7 +239,7 @@ extern "C" int stzs_istft_stream_span(int f0, int Fc, int final_chunk, int n_fft
 }
 
 extern "C" int stzs_istft_stream(const stzs_istft_stream_args* a, void* stream) {
-    if (!a || !a->post || !a->wav) return STZS_EINVAL;
+    if (!a || !a->post || !a->wav || !stzs_aligned(a->lens, 4) || !stzs_aligned(a->post_off, 4)) return STZS_EINVAL;
     if (a->B <= 0 || a->f0 < 0 || a->Fc <= 0 || bad_geom(a->n_fft, a->hop_s) || bad_size(a->n_fft) ||
         a->ldp < a->n_fft + 2)
         return STZS_ESHAPE;
@@ -216,6 +248,8 @@ extern "C" int stzs_istft_stream(const stzs_istft_stream_args* a, void* stream) 
     if (a->final_chunk && a->f0 + a->Fc < 2) return STZS_ESHAPE;
     if (a->tail_in && a->tail_in == a->tail_out) return STZS_EINVAL;  // block 0 writes while others read
     IstftJob j{};
+    j.lens = a->lens;
+    j.post_off = a->post_off;
     j.post = a->post;
     j.tail_in = a->f0 > 0 ? a->tail_in : nullptr;
     j.tail_out = a->tail_out;

@@ -155,7 +155,8 @@ class FrameRowsArgs(C.Structure):
 class IstftStreamArgs(C.Structure):
     _fields_ = [("post", vp), ("tail_in", vp), ("tail_out", vp), ("wav", vp),
                 ("ldp", i64), ("bsp", i64), ("bsw", i64), ("ldt", i64),
-                ("B", i32), ("f0", i32), ("Fc", i32), ("final_chunk", i32), ("n_fft", i32), ("hop_s", i32)]
+                ("B", i32), ("f0", i32), ("Fc", i32), ("final_chunk", i32), ("n_fft", i32), ("hop_s", i32),
+                ("lens", opt_vp), ("post_off", opt_vp)]  # optional int32 [B]: absolute frames / first post row per utterance
 
 
 class FramesArgs(C.Structure):

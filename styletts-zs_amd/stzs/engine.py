@@ -240,6 +240,20 @@ def check_ref_lens(ref_lens, B: int, N: int, n_fft: int) -> torch.Tensor:
     return t.to(torch.int32)
 
 
+def check_frame_lens(frame_lens, B: int, T40: int) -> list:
+    """the ragged chunked decoder's per-row frame counts as host integers -> list of B ints.  frame_lens: a sequence or
+    a host tensor of B integers, each in [1, T40] (T40 the padded width), anything else raises ValueError; or a device
+    tensor, read back here -- ONE host sync, the window schedule is made on the host -- and checked the same way."""
+    t = torch.as_tensor(frame_lens)
+    if t.device.type != "cpu":
+        t = t.cpu()
+    if t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"frame_lens must be {B} integers (one per row), got {tuple(t.shape)} {t.dtype}")
+    if B and (int(t.min()) < 1 or int(t.max()) > T40):
+        raise ValueError(f"frame_lens must lie in [1, {T40}] (the padded width), got {t.tolist()}")
+    return [int(v) for v in t.tolist()]
+
+
 def sigma_schedule(spec: Spec, steps: int):
     """Distilled pins 1: [smax, 0], 2: [smax, 0.5, 0]; otherwise Karras(rho) + trailing 0 (a1)."""
     if steps == 1:
@@ -387,6 +401,7 @@ class StyleTTSZS:
         # graph-replayed); check_status() reads it and raises
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.prompt_idx = None  # discrete prompt codes of the last prompt_encode (device int32 [B, L_s, G])
+        self.frame_lens = None  # frame counts of the last synth_stream(ragged_frames=True) (device int32 [B])
 
     def check_status(self, reset=True):
         """raise RuntimeError if any LSTM exchange since the last check timed out (its h-states are wrong).
@@ -1663,13 +1678,15 @@ class StyleTTSZS:
                   collect=collect, what=key + ".conv2", **({} if flens is None else dict(t_lens=flens, t_lens_mul=fmul)))
 
     # ------------------------------------------------------------------ (c) decoder
-    def decode(self, pro: dict, codes: torch.Tensor, seeds, istft=True, frame_lens=None, trace=None) -> torch.Tensor:
+    def decode(self, pro: dict, codes: torch.Tensor, seeds, istft=True, frame_lens=None, trace=None,
+               rows=None) -> torch.Tensor:
         """a9-a13: decoder pre-blocks, generator, conv_post + iSTFT.  pro: asr_buf (aligned text features in the
         decoder input buffer), F0 / N [B, T80], T40 -> wav fp32 [B, 600 T40] (or conv_post rows, istft=False).
         frame_lens (int32 [B] device tensor, the ragged decoder): row b holds frame_lens[b] of the T40
         frames -- the alignment's totals, predict_prosody(ragged_frames=True)["frame_lens"] -- and is computed as
         alone at T40 = frame_lens[b]: wav[b, :600 frame_lens[b]] are those bits, the tail exact zeros; no host sync.
-        trace (a dict): the stages' activations (generator())."""
+        rows: frame_rows(frame_lens, T40) where the caller made them already (synth_stream hands their last array to the
+        streaming iSTFT).  trace (a dict): the stages' activations (generator())."""
         if frame_lens is None:
             # the harmonic source depends on F0 only: forkable beside the decoder pre-blocks (fork site "src")
             (gen_in, gbd), har = self.fork("src", lambda: self.decoder_pre(pro, codes),
@@ -1678,7 +1695,8 @@ class StyleTTSZS:
                 trace["gen_in"] = gen_in
             return self.generator(gen_in, pro["F0"], seeds, gbd, trace=trace, istft=istft, har=har)
         self._check_ragged_decoder()
-        rows = self.frame_rows(frame_lens, pro["T40"])  # (on the current stream, before the fork: both branches wait)
+        if rows is None:
+            rows = self.frame_rows(frame_lens, pro["T40"])  # (on the current stream, before the fork: both branches wait)
         (gen_in, gbd), har = self.fork("src", lambda: self.decoder_pre(pro, codes, frame_lens),
                                        lambda: self.sine_gen(pro["F0"], seeds, rows[0]))
         if trace is not None:
@@ -1862,11 +1880,13 @@ class StyleTTSZS:
                   refl=1 if last else 0, res=xsrc, what=f"ups{i}", **rg)
         return xu
 
-    def conv_post(self, x: Act, rows=None) -> Act:
+    def conv_post(self, x: Act, rows=None, out: Act = None) -> Act:
         """LeakyReLU(0.01) + conv_post (128 -> 22, k7) -> fp32 rows [B, Tf, 22] (log-magnitude | phase argument).
-        rows (int32 [B] device tensor, the ragged decoder): the rows of x each utterance holds."""
+        rows (int32 [B] device tensor, the ragged decoder): the rows of x each utterance holds.
+        out: the caller's fp32 rows [B, Tf, >= 22] instead of the engine's buffer (the ragged chunked decoder's)."""
         S, W = self.spec, self.W
-        post = self.act("gen.post", x.B, x.T, S.har_ch, torch.float32)
+        post = out if out is not None else self.act("gen.post", x.B, x.T, S.har_ch, torch.float32)
+        assert post.B == x.B and post.T == x.T and post.t.dtype == torch.float32
         self.conv(W.conv_post, x, Act(post.t, 0, S.har_ch), pad=3, pro_act=L.ACT_LEAKY, pro_slope=0.01,
                   what="conv_post", **({} if rows is None else dict(t_lens=rows, t_lens_rows=1)))
         return post
@@ -1887,10 +1907,12 @@ class StyleTTSZS:
         self._call(self.lib.stzs_istft, a, "istft", cost=(0, B * Tcur * S.har_ch * 4 + B * Nout * 4))
         return wav
 
-    def generator(self, x: Act, F0: torch.Tensor, seeds, gbd, trace=None, istft=True, har: Act = None, rows=None):
+    def generator(self, x: Act, F0: torch.Tensor, seeds, gbd, trace=None, istft=True, har: Act = None, rows=None,
+                  post_out: Act = None):
         """a10-a13: harmonic source, per stage the noise conv + ConvTranspose up-sampling and the MRF, then
         conv_post and the iSTFT.  har: precomputed harmonic-source features (the chunked decoder's window slice).
-        rows (frame_rows(), the ragged decoder): the row counts of x ([0]) and of every stage's output ([1 + i])."""
+        rows (frame_rows(), the ragged decoder): the row counts of x ([0]) and of every stage's output ([1 + i]).
+        post_out: conv_post's rows go there (conv_post(out=...))."""
         S, W = self.spec, self.W
         ng = W.dec_norm
         rw = (lambda k: None) if rows is None else (lambda k: rows[k])
@@ -1905,16 +1927,18 @@ class StyleTTSZS:
             x = self.mrf(xu, i, gbd, ng, rw(1 + i))
             if trace is not None:
                 trace[f"mrf_out{i}"] = x
-        post = self.conv_post(x, rw(len(S.up_rates)))
+        post = self.conv_post(x, rw(len(S.up_rates)), post_out)
         if trace is not None:
             trace["post"] = post
         if not istft:
             return post
         return self.istft(post, rw(len(S.up_rates)))
 
-    def _istft_chunk(self, rows_ptr, ldp, bsp, B, f0, Fc, fin, wav, tails, i):
+    def _istft_chunk(self, rows_ptr, ldp, bsp, B, f0, Fc, fin, wav, tails, i, lens=None, post_off=None):
         """one streaming-iSTFT launch: conv_post frames [f0, f0 + Fc) at rows_ptr (row pitch ldp, batch stride bsp,
-        fp32) -> samples [n0, n1) of wav [B, Nout], the 3-frame tail carried in the ping-pong buffers.  -> (n0, n1)"""
+        fp32) -> samples [n0, n1) of wav [B, Nout], the 3-frame tail carried in the ping-pong buffers.  -> (n0, n1)
+        lens / post_off (int32 [B] device tensors, ragged streaming): each row's absolute frame count and the row of
+        rows_ptr + b * bsp its chunk frames start at (stzs_istft_stream_args)."""
         S = self.spec
         n0, n1 = C.c_int64(), C.c_int64()
         halo = self.lib.stzs_istft_stream_span(f0, Fc, fin, S.n_fft, S.istft_hop, C.byref(n0), C.byref(n1))
@@ -1927,6 +1951,10 @@ class StyleTTSZS:
         a.wav = wav.data_ptr() + n0.value * 4
         a.ldp, a.bsp, a.bsw, a.ldt = ldp, bsp, wav.shape[1], tails[0].shape[2]
         a.B, a.f0, a.Fc, a.final_chunk, a.n_fft, a.hop_s = B, f0, Fc, fin, S.n_fft, S.istft_hop
+        if lens is not None:
+            a.lens = lens.data_ptr()
+        if post_off is not None:
+            a.post_off = post_off.data_ptr()
         self._call(self.lib.stzs_istft_stream, a, "istft_stream")
         return n0.value, n1.value
 
@@ -1942,8 +1970,18 @@ class StyleTTSZS:
             out.append((a, min(a + chunk, T40), wa, wa + W))
         return out
 
+    @staticmethod
+    def ragged_chunk_windows(frame_lens, chunk: int, halo: int):
+        """the ragged chunked decoder's schedule (host arithmetic): row b of the batch keeps its OWN schedule
+        chunk_windows(T_b, chunk, halo); batch chunk k, owning the aligned frames [k chunk, (k + 1) chunk), holds the
+        rows that still have a window there (k chunk < T_b).  -> one list per batch chunk, ceil(max T_b / chunk) of
+        them, of (row, (a, b, wa, wb)) in row order."""
+        per_row = [StyleTTSZS.chunk_windows(int(T_b), chunk, halo) for T_b in frame_lens]
+        n = max((len(w) for w in per_row), default=0)
+        return [[(b, w[k]) for b, w in enumerate(per_row) if k < len(w)] for k in range(n)]
+
     def decode_chunked(self, pro: dict, codes: torch.Tensor, seeds, chunk: int, halo: int, batch_windows=True,
-                       max_pass_rows: int = 64):
+                       max_pass_rows: int = 64, frame_lens=None):
         """configs[4] CHUNKED streaming decoder (oracle/stzs_ref.py decode_chunked): each chunk of `chunk` aligned
         frames is decoded over its fixed-length window (chunk_windows) -- pre-blocks and generator on the window alone,
         AdaIN with WINDOW-local InstanceNorm statistics -- on the slice of the whole utterance's harmonic-source
@@ -1956,7 +1994,17 @@ class StyleTTSZS:
         a pass's audio is ready only when the whole pass is decoded and its activations scale with its rows, so at large
         B or long targets the later windows go in several passes (time to the second chunk ~ one pass's decode; peak
         activation memory ~ max_pass_rows windows).  Yields (first_sample, wav chunk [B, n]) views of one [B, 600 T40]
-        buffer."""
+        buffer.
+        frame_lens (ragged streaming): the rows' frame counts T_b as HOST integers -- a list or CPU
+        tensor, each in [1, T40], range-checked before any launch; a device tensor is read back once (one host sync:
+        the window schedule is made on the host).  Row b keeps the schedule chunk_windows(T_b, chunk, halo) and its
+        samples [0, 600 T_b) are the bits of this call on the row alone at T40 = T_b, exact zeros from there; the
+        chunks tile [0, 600 max T_b) (_decode_chunked_ragged)."""
+        if frame_lens is not None:
+            self._check_ragged_decoder()
+            yield from self._decode_chunked_ragged(pro, codes, seeds, int(chunk), int(halo), batch_windows,
+                                                   max_pass_rows, frame_lens)
+            return
         S = self.spec
         enc_in, F0, Nn, T40 = pro["asr_buf"], pro["F0"], pro["N"], pro["T40"]
         B = enc_in.B
@@ -2023,11 +2071,152 @@ class StyleTTSZS:
                                            fpf * a0, fpf * (b0 - a0) + fin, fin, wav, tails, k)
                 yield n0, wav[:, n0:n1]
 
-    def istft_stream(self, post: Act, chunk_frames: int):
+    def _decode_chunked_ragged(self, pro, codes, seeds, chunk, halo, batch_windows, max_pass_rows, frame_lens):
+        """decode_chunked on a ragged batch (ragged_chunk_windows).  The harmonic source is computed once, ragged.  A
+        pass holds only the (utterance, window) rows that exist, utterance-major, at the width of its longest window,
+        and is decoded through the ragged decoder on the window lengths (frame_rows, decoder_pre(frame_lens),
+        generator(rows)): a window is computed as alone, with window-local statistics.  Each batch chunk is ONE
+        stzs_istft_stream launch over all B rows: lens = 120 T_b + 1 finalises a row by its own count, post_off points
+        a row at its own window's frames, a finished row gets zeros.  A row whose T_b is a multiple of `chunk` has its
+        last frame (120 T_b) read by the NEXT batch chunk's launch, from the window that computed it: where that
+        window belongs to an earlier pass, the frame is kept in a spare row in front of the pass's conv_post rows.
+        The pass's two int32 tables (window lengths, post_off per chunk) are built on the host and uploaded once."""
+        enc_in, F0, Nn, T40 = pro["asr_buf"], pro["F0"], pro["N"], int(pro["T40"])
+        B = enc_in.B
+        Tb = check_frame_lens(frame_lens, B, T40)  # (before any launch; a device tensor: the one host read)
+        S, dev = self.spec, self.device
+        if isinstance(frame_lens, torch.Tensor) and frame_lens.device.type != "cpu":
+            fl = frame_lens.to(torch.int32).contiguous()
+        else:
+            fl = torch.tensor(Tb, dtype=torch.int32).to(dev)
+        fpf = S.frame40 // S.istft_hop
+        assert fpf == 2 * math.prod(S.up_rates)
+        full = self.frame_rows(fl, T40)
+        har = self.sine_gen(F0, seeds, full[0])
+        lens_abs = full[-1].clone()  # fpf T_b + 1 (the passes' frame_rows reuse the buffer)
+        Tm = max(Tb)
+        wav = self.buf("gen.wav_chunked", (B, T40 * S.frame40), torch.float32)
+        ncol = _rup(S.n_fft + 2, 4)
+        tails = [self.buf("gen.ctail0", (B, 8, ncol), torch.float32), self.buf("gen.ctail1", (B, 8, ncol), torch.float32)]
+        dt = self.dec_dt
+        sched = self.ragged_chunk_windows(Tb, chunk, halo)
+        nck = len(sched)
+        if batch_windows:
+            per = max(1, max_pass_rows // max(B, 1))  # batch chunks per pass after the first
+            rest = list(range(1, nck))
+            groups = [[0]] + [rest[i:i + per] for i in range(0, len(rest), per)]
+        else:
+            groups = [[k] for k in range(nck)]
+        groups = [g for g in groups if g]
+        # per pass: its rows, utterance-major -- (utterance, [(batch chunk, window)])
+        passes = []
+        for ks in groups:
+            byrow = {}
+            for k in ks:
+                for b, w in sched[k]:
+                    byrow.setdefault(b, []).append((k, w))
+            passes.append(sorted(byrow.items()))
+        ldp = _rup(S.har_ch, 8)
+        nsp = _rup(B, 4)  # spare rows in front: utterance b's last frame, carried from an earlier pass
+        cap = max(sum(len(v) for _, v in p) * (fpf * max(w[3] - w[2] for _, v in p for _, w in v) + 1) for p in passes)
+        pw = self.buf("gen.post_w", (nsp + cap, ldp), torch.float32, zero=True)
+        F0c, Nc = F0.contiguous(), Nn.contiguous()
+        cdt = L.F32 if codes.dtype == torch.float32 else L.BF16
+        esz, hsz = enc_in.t.element_size(), har.t.element_size()
+        last_row = {}  # utterance -> row of pw that holds its frame fpf T_b, where the next pass's first launch reads it
+        for ks, rows_p in zip(groups, passes):
+            Bw = sum(len(v) for _, v in rows_p)
+            Wn = max(w[3] - w[2] for _, v in rows_p for _, w in v)
+            Tfw = fpf * Wn + 1
+            # ---- the host tables of the pass: window lengths [Bw], then post_off [len(ks)][B]
+            wl, ridx, r = [], {}, 0
+            for b, v in rows_p:
+                for k, w in v:
+                    wl.append(w[3] - w[2])
+                    ridx[(k, b)] = r
+                    r += 1
+            offs = []
+            for k in ks:
+                for b in range(B):
+                    if (k, b) in ridx:
+                        a0, _, wa, _ = dict(sched[k])[b]
+                        offs.append(nsp + ridx[(k, b)] * Tfw + fpf * (a0 - wa))
+                    elif Tb[b] == chunk * k:  # its last frame is this launch's first
+                        if (k - 1, b) in ridx:
+                            offs.append(nsp + ridx[(k - 1, b)] * Tfw + fpf * min(chunk + 2 * halo, Tb[b]))
+                        else:
+                            assert b in last_row
+                            offs.append(b)  # (its spare row, filled below)
+                    else:
+                        offs.append(0)  # finished: nothing is read
+            tab = torch.tensor(wl + offs, dtype=torch.int32).to(dev)
+            wl_d = tab[:Bw]
+            # ---- window rows: zeros past a window's own rows (the harmonic-source rows there are the noise convs' padding)
+            enc_w = self.act("dec.enc_in_w", Bw, Wn, S.d_txt + 2, dt)
+            hb = self.buf("gen.har_w", (Bw, self._har_rows(Tfw), har.ld), dt, zero=True)
+            F0w = self.buf("dec.F0w", (Bw, 2 * Wn), torch.float32, zero=True)
+            Nw = self.buf("dec.Nw", (Bw, 2 * Wn), torch.float32, zero=True)
+            for t in (enc_w.t, hb, F0w, Nw):
+                t.zero_()
+            har_w = Act(hb[:, :Tfw], 0, S.har_ch)
+            whole = Bw == B and all(len(v) == 1 for _, v in rows_p)  # every utterance once: its codes as they are
+            cw_ = codes if whole else self.buf("dec.codes_w", (Bw,) + tuple(codes.shape[1:]), codes.dtype)
+            row = 0
+            for b, v in rows_p:
+                Wb = v[0][1][3] - v[0][1][2]  # (one window length per utterance)
+                nw = len(v)
+                i = 0
+                while i < nw:  # runs of windows whose starts are `chunk` apart: one strided copy per run and tensor
+                    j = i + 1
+                    while j < nw and v[j][1][2] - v[j - 1][1][2] == chunk:
+                        j += 1
+                    wa, cnt = v[i][1][2], j - i
+                    self._copy_rows(enc_in.t.data_ptr() + (b * enc_in.bs + wa * enc_in.ld) * esz, enc_in.ld,
+                                    chunk * enc_in.ld, enc_w.t.data_ptr() + (row + i) * enc_w.bs * esz, enc_w.ld,
+                                    enc_w.bs, cnt, Wb, S.d_txt, enc_in.dt, enc_w.dt)
+                    self._copy_rows(har.t.data_ptr() + (b * har.bs + fpf * wa * har.ld) * hsz, har.ld,
+                                    fpf * chunk * har.ld, har_w.t.data_ptr() + (row + i) * har_w.bs * hsz, har_w.ld,
+                                    har_w.bs, cnt, fpf * Wb + 1, S.har_ch, har.dt, har_w.dt)
+                    for src, dst in ((F0c, F0w), (Nc, Nw)):
+                        self._copy_rows(src.data_ptr() + (b * src.stride(0) + 2 * wa) * 4, 2 * Wb, 2 * chunk,
+                                        dst.data_ptr() + (row + i) * 2 * Wn * 4, 2 * Wb, 2 * Wn, cnt, 1, 2 * Wb,
+                                        L.F32, L.F32)
+                    i = j
+                if not whole:  # every window of utterance b takes its codes (source block stride 0)
+                    Lc, Dc = codes.shape[1], codes.shape[2]
+                    self._copy_rows(codes.data_ptr() + b * codes.stride(0) * codes.element_size(), Dc, 0,
+                                    cw_.data_ptr() + row * Lc * Dc * cw_.element_size(), Dc, Lc * Dc, nw, Lc, Dc,
+                                    cdt, cdt)
+                row += nw
+            # ---- the carried last frames move before conv_post overwrites the rows they lie in
+            for b, src in last_row.items():
+                self._copy_rows(pw.data_ptr() + src * ldp * 4, ldp, 0, pw.data_ptr() + b * ldp * 4, ldp, 0, 1, 1, ldp,
+                                L.F32, L.F32)
+            rows = self.frame_rows(wl_d, Wn)
+            gen_in, gbd = self.decoder_pre(dict(asr_buf=enc_w, F0=F0w, N=Nw, T40=Wn), cw_, wl_d)
+            post = Act(pw[nsp:nsp + Bw * Tfw].view(Bw, Tfw, ldp), 0, S.har_ch)
+            self.generator(gen_in, F0w, seeds, gbd, istft=False, har=har_w, rows=rows, post_out=post)
+            # an utterance that ends with this pass's last batch chunk, on the chunk boundary: the next pass reads its
+            # last frame
+            last_row = {b: nsp + ridx[(v[-1][0], b)] * Tfw + fpf * (v[-1][1][3] - v[-1][1][2]) for b, v in rows_p
+                        if Tb[b] == chunk * (ks[-1] + 1) and ks[-1] + 1 < nck}
+            for i, k in enumerate(ks):
+                a0 = chunk * k
+                b0 = min(a0 + chunk, Tm)
+                fin = int(b0 == Tm)
+                n0, n1 = self._istft_chunk(pw.data_ptr(), ldp, 0, B, fpf * a0, fpf * (b0 - a0) + fin, fin, wav, tails,
+                                           k, lens_abs, tab[Bw + i * B:Bw + (i + 1) * B])
+                yield n0, wav[:, n0:n1]
+
+    def istft_stream(self, post: Act, chunk_frames: int, lens=None):
         """iSTFT of conv_post frames [B, Tf, 22] in chunks of `chunk_frames` frames,
         the 3-frame tail carried between chunks (ping-pong buffers).  Yields (n0, wav[:, n0:n1]) as each
         chunk is enqueued; the views are slices of one [B, Nout] buffer, so no chunk overwrites another,
-        and their concatenation is bit-identical to the whole-utterance iSTFT."""
+        and their concatenation is bit-identical to the whole-utterance iSTFT.
+        lens (int32 [B] device tensor, ragged streaming): each row's iSTFT frames -- the last array of
+        frame_rows().  The chunk spans stay those of the padded Tf; row b's samples below (lens[b] - 1) hop_s are the
+        bits of istft(lens=...) -- of the row alone --, exact zeros from there, each row finalised by its own count in
+        whatever chunk its last samples fall into.  No host sync."""
         S = self.spec
         B, Tf = post.B, post.T
         Nout = (Tf - 1) * S.istft_hop
@@ -2040,7 +2229,7 @@ class StyleTTSZS:
             if 0 < Tf - f0 - Fc < 2:  # fold a 1-frame remainder (Tf = 600*T40/5 + 1) into this chunk
                 Fc = Tf - f0
             n0, n1 = self._istft_chunk(post.ptr + f0 * post.ld * 4, post.ld, post.bs, B, f0, Fc, int(f0 + Fc == Tf),
-                                       wav, tails, i)
+                                       wav, tails, i, lens)
             yield n0, wav[:, n0:n1]
             f0 += Fc
             i += 1
@@ -2253,24 +2442,40 @@ class StyleTTSZS:
 
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
                      codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None,
-                     text_lens=None, ref_lens=None):
+                     text_lens=None, ref_lens=None, ragged_frames=False):
         """configs[4] long-form synthesis with the streaming iSTFT decoder: the text,
         style, prosody and conv stack run over the whole target (AdaIN instance statistics are
         utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
         (first_sample, wav_chunk [B, n]) device views; their concatenation equals synth()["wav"].
         chunked_halo=H: the CHUNKED decoder instead (decode_chunked: every `chunk_s` chunk decoded over a window of
         +-H aligned frames with window-local statistics -- a different function, parity vs oracle decode_chunked):
-        the first chunk is ready after the front and one window's decode."""
+        the first chunk is ready after the front and one window's decode.
+        ragged_frames=True: the rows need not share their frame count, as synth(ragged_frames=True) --
+        ragged prosody, the ragged decoder, the streaming iSTFT on the rows' own frame counts.  The same pairs over the
+        padded width; the device frame counts (int32 [B]) are in self.frame_lens from the first yield on: row b is
+        valid to 600 frame_lens[b] -- the bits of the row's own stream -- and exact zeros from there.  No host sync is
+        added, but for the chunked decoder: it reads the frame counts back once (its window schedule is host work)
+        and its chunks tile [0, 600 max frame_lens)."""
+        if ragged_frames:
+            self._check_ragged_decoder()
         S = self.spec
         _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                              n_frames, prompt_idx, text_lens, ref_lens)
+                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames)
+        fl = None
+        if ragged_frames:
+            fl = self.frame_lens = pro["frame_lens"]
         if chunked_halo is not None:  # the chunked decoder: chunk-local statistics, first audio after one window
             yield from self.decode_chunked(pro, codes, seeds, max(1, int(round(chunk_s * S.sr / S.frame40))),
-                                           int(chunked_halo))
+                                           int(chunked_halo), **({} if fl is None else dict(frame_lens=fl)))
         else:
-            post = self.decode(pro, codes, seeds, istft=False)
             frames = max(1, int(round(chunk_s * S.sr / S.istft_hop)))
-            yield from self.istft_stream(post, frames)
+            if fl is None:
+                post = self.decode(pro, codes, seeds, istft=False)
+                yield from self.istft_stream(post, frames)
+            else:
+                rows = self.frame_rows(fl, pro["T40"])
+                post = self.decode(pro, codes, seeds, istft=False, frame_lens=fl, rows=rows)
+                yield from self.istft_stream(post, frames, lens=rows[-1])
         if check and not self._capturing():
             self.check_status()
 
