@@ -202,7 +202,11 @@ size_t stzs_conv_splitk_workspace(int64_t rows, int32_t co_pad, int32_t splitk);
  * then lo = bf16(w - hi)), each [co_pad/128][ci_pad/32 * ks][128][32] in the STZS_PACK_KSTEP swizzle with
  * cic = 32 (stzs/weights.py kstep_stream_x3); activations are split the same way when staged, and every
  * product is ah*bh + ah*bl + al*bh on bf16 MFMA with fp32 accumulation (~fp32 accuracy at ~3x bf16 work).
- * Requires cic = 32; any in/out dtype; the accurate (libm) prologue activations. */
+ * Requires cic = 32; any in/out dtype; the accurate (libm) prologue activations.
+ * Memory contract as checked by tests/test_gpu_precise_probe.py (fp32 in and out): x is read only at rows [0, T_in) of
+ * each utterance and columns [0, ceil8(Ci)) (finite values in [Ci, ceil8(Ci))), the prologue rows only at [0, Ci) with
+ * the strides given, y is written only at its [T_out (ups: T_final + refl)] x [Co] elements, stat_part only at the
+ * 64-row chunks of T_out and columns [0, Co). */
 #define STZS_CONV_W_X3 1024
 /* flags bit: SMALL-M linear on the whole chip (csrc/rows.hip; the batch-1 denoiser linears): bf16 (or fp32, scaled by
  * pro_cscale and rounded to bf16) x rows, STZS_PACK_KSTEP weights; every workgroup owns 16 output columns, all rows of
@@ -235,7 +239,13 @@ size_t stzs_conv_splitk_workspace(int64_t rows, int32_t co_pad, int32_t splitk);
  * [2][4 waves][2][64 lanes][8] bf16 of the STZS_CONV_W_FRAG32 layout (same frag32 row permutation; stzs/weights.py
  * frag32x3_stream, STZS_PACK_FRAG32X3).  cic = 128, ks in {3, 7, 11} (Snake) or 3 (LeakyReLU / identity, no
  * accumulate input), stride 1, fp32 x / y / res / acc_in (32-B aligned rows), Co % 8 == 0; the InstanceNorm
- * statistics are those of the stored fp32 values. */
+ * statistics are those of the stored fp32 values.
+ * Memory contract as checked by tests/test_gpu_precise_probe.py: x is read only at rows [0, T_in) of each utterance
+ * (the FLAT linear: flat rows [0, B T_in), located by bsx) and columns [0, ceil8(Ci)) -- values in [Ci, ceil8(Ci)) must
+ * be finite, they are multiplied by 0 --, the prologue rows only at [0, Ci) with stat_bs / gb_bs / gb_beta_off as given,
+ * res / acc_in only at the rows and columns of y with their own ldr / lda / bsr / bsa (bsr = 0: one residual for all
+ * utterances), y is written only at [T_out] x [Co] (the narrow form: not at [Co, ceil8(Co))), stat_part only at the
+ * 64-row chunks of T_out and columns [0, Co). */
 #define STZS_CONV_W_FRAG32X3 16384
 /* flags bit (FRAG32 weights, Snake prologue): keep the register-direct MRF conv's 128-row time tiles where its
  * launcher would take 64-row tiles (grids of fewer than two 128-row tiles per CU, e.g. batch 1).  Bit-identical either

@@ -14,7 +14,8 @@
 //  * staged rows at a 256-B pitch with the 16-B chunk of channel group c of row r at position c ^ (r & 15): the
 //    ds_read_b128 B-fragment reads (16 consecutive rows x 4 channel groups per wave-instruction) are bank-conflict
 //    free without padding, so a 146-row tile pair (hi + lo) takes 73 KB and two workgroups fit a CU.  Tiles whose
-//    halo would exceed that (k7 d5, k11 d3 / d5) run as 64-row tiles;
+//    halo'd rows exceed what a thread stages (16 sb_rows(ks, 128): k11 d3 / d5) run as 64-row tiles; k7 d5 (158 rows
+//    <= 160) keeps the 128-row tile, 82 944 B of LDS: one workgroup per CU;
 //  * epilogue straight from the accumulators (lane (g, n): 8 consecutive channels of one time row, 32-B fp32 loads /
 //    stores), fused InstanceNorm statistics of the stored fp32 values per 64-row chunk (the stzs_chan_stats partial
 //    layout, as mrfv / conv_x3).

@@ -1112,3 +1112,569 @@ def lin_y_layout(c, poisoned, dev="cpu"):
     if poisoned:
         return guarded((c.B, c.T, c.Co), c.ypads, LIN_SENT[dt], dt, dev)
     return guarded((c.B, c.T, c.Co), (0, 0, 0), 0.0, dt, dev)
+
+
+# ---- the precise (split-operand) convs: exact probes and exact-sum dense checks (tests/test_gpu_precise_probe.py,
+# test_refops_x3.py, the --precise-cases mode of tools/dispatch_trace.py) ----
+# The precise kernels (csrc/mrfx.hip mrfx_conv / mrfx_lin, csrc/convx.hip conv_x3) split every fp32 operand into hi =
+# bf16(z), lo = bf16(z - hi) and form w z as wl zh + wh zl + wh zh on the bf16 MFMA with fp32 accumulation (wl zl is
+# dropped).  hi + lo is exactly representable in fp32, so a one-hot weight 1.0 reads the staged PAIR out bit for bit; and
+# with operands a + b 2^-10 (small integers a, |b| <= 3) every product and partial sum is a multiple of 2^-10 below 2^13:
+# any accumulation order gives the same bits, equal to the fp64 sum of the three products.
+
+PX_POISON = 2.0 ** 100          # finite: 0 * poison = 0, and mrfx_conv's x * 0 of the channels [Ci, ceil8(Ci))
+PX_SENT = 0x7FC0A5A5            # the NaN payload of the output guards
+PX_XPADS, PX_YPADS = (3, 8, 8), (2, 8, 8)   # guarded()'s pads: every pitch a multiple of 8 floats, 32-byte bases
+
+# prologues: (AdaIN: None | "p2" (power-of-two sc, sh = 0) | "gen", activation, slope, exact?) -- the table of
+# tests/test_gpu_conv_probe.py PRO
+PX_PRO = {
+    "none": (None, None, 0.0, True),
+    "adain2": ("p2", None, 0.0, True),
+    "adain2_leaky8": ("p2", "leaky", 0.125, True),
+    "leaky8": (None, "leaky", 0.125, True),
+    "leaky.1": (None, "leaky", 0.1, False),
+    "leaky.01": (None, "leaky", 0.01, False),
+    "adain_leaky.2": ("gen", "leaky", 0.2, False),
+    "snake": ("gen", "snake", 0.0, False),
+    "leaky2": (None, "leaky", 2.0, True),  # (the exact-sum launches: negative values doubled, the 2^-10 grid kept)
+}
+
+
+def split_ref(z):
+    """fp32 -> (hi, lo, S) fp32: hi = bf16(z) to nearest even, lo = bf16(z - hi) (the difference is exact), S = hi + lo
+    (exact in fp32: lo's lowest bit is not below z's)"""
+    z = z.float()
+    hi = z.to(torch.bfloat16).float()
+    lo = (z - hi).to(torch.bfloat16).float()
+    return hi, lo, hi + lo
+
+
+def x3_prologue32(x, sc=None, sh=None, act=None, slope=0.0):
+    """the fp32 prologue value of the exact prologues (no AdaIN: sc 1, sh 0; power-of-two AdaIN; LeakyReLU with a
+    power-of-two slope): x sc + sh, then the activation, every step exact -> fp32 [B, T, C].  (-0 becomes +0: -0 + 0.)"""
+    x = x.float()
+    one = torch.ones(x.shape[0], x.shape[2])
+    sc = one if sc is None else sc.float()
+    sh = 0 * one if sh is None else sh.float()
+    v = x * sc[:, None, :] + sh[:, None, :]
+    if act == "leaky":
+        v = torch.where(v >= 0, v, v * slope)
+    else:
+        assert act is None, act
+    return v
+
+
+def x3_identity_expect(x, sc=None, sh=None, act=None, slope=0.0):
+    """what a precise conv with a one-hot weight 1.0 must read out for an exact prologue: S = hi + lo of the exact fp32
+    prologue value (the kernel computes 0 + wl zh (= 0) + wh zl + wh zh) -> fp32 [B, T, C]"""
+    return split_ref(x3_prologue32(x, sc, sh, act, slope))[2]
+
+
+def _epilogue64(y, t, b, gate, res, res_tdiv, out_scale, acc_in, beta):
+    """((y + b) gate + res) out_scale + beta acc_in on the values y and on the magnitudes t -> (y, t) fp64"""
+    rep = lambda r: r.double().repeat_interleave(res_tdiv, dim=1)[:, :y.shape[1]] if res_tdiv > 1 else r.double()
+    if b is not None:
+        y, t = y + b.double(), t + b.double().abs()
+    if gate is not None:
+        y, t = y * gate.double()[:, None, :], t * gate.double().abs()[:, None, :]
+    if res is not None:
+        y, t = y + rep(res), t + rep(res).abs()
+    y, t = y * out_scale, t * abs(out_scale)
+    if acc_in is not None:
+        y, t = y + beta * acc_in.double(), t + abs(beta) * acc_in.double().abs()
+    return y, t
+
+
+def x3_terms_ref(zh, zl, wh, wl, b, *, pad=0, dil=1, stride=1, res=None, res_tdiv=1, out_scale=1.0, acc_in=None,
+                 beta=0.0, gate=None, ups=0, ups_pad=0, refl=0, lolo=False):
+    """conv_terms_ref on the kernel's three products, in fp64: wl zh + wh zl + wh zh (wl zl excluded; lolo: included,
+    for the self-checks), then the epilogue once.  zh / zl [B, T, Ci] the staged planes, wh / wl the weight's planes in
+    the conv's (or ConvTranspose's) weight layout -> (y, terms) [B, T_out, Co] fp64, terms on absolute values."""
+    kw = dict(pad=pad, dil=dil, stride=stride, ups=ups, ups_pad=ups_pad, refl=refl)
+    y = t = 0.0
+    for x, w in ((zh, wl), (zl, wh), (zh, wh)) + (((zl, wl),) if lolo else ()):
+        yy, tt = conv_terms_ref(x, w, None, **kw)
+        y, t = y + yy, t + tt
+    return _epilogue64(y, t, b, gate, res, res_tdiv, out_scale, acc_in, beta)
+
+
+def exact_sum_case(K, seed, *, B, T, Ci, Co, k=1, T_out=None, alpha=1.0, beta=0.0, res=False, res_tdiv=1, res_B=None,
+                   acc=False, gate=False, zscale=1):
+    """operands of an exact-sum launch: x [B, T, Ci] and w [Co, Ci, k] hold a + b 2^-10 with integers |a| <= 2 (<= 1
+    where K = Ci k > 1408) and |b| <= 3 (b = 3 sign(a) instead of -3 sign(a) where |a| = 1), so hi = a and lo = b 2^-10; one value in
+    eight is an exact zero (a = 0 never meets b != 0: hi would be b 2^-10); bias, residual and accumulate input small integers, alpha in {1, 0.5}, beta in {1, 2}, gates
+    in {1, 2, -1}; zscale: the largest factor an exact prologue applies to x (2 for LeakyReLU with slope 2).  Every product (wl zl is never formed) and every partial sum in any order is then a multiple of 2^-g,
+    g = 10 (11 with alpha = 0.5).  The condition of the case, asserted here on its worst case: (sum |w||z| + |bias| +
+    |res| + |beta acc|) 2^g < 2^24 -- every intermediate is exactly representable in fp32.
+    -> dict(x, w, b, res, acc, gate, alpha, beta)"""
+    assert K == Ci * k and alpha in (1.0, 0.5) and beta in (0.0, 1.0, 2.0)
+    amax = 2 if K <= 1408 else 1
+    g = torch.Generator().manual_seed(seed)
+
+    def val(*s):
+        a, b = torch.randint(1, amax + 1, s, generator=g) * (2 * torch.randint(0, 2, s, generator=g) - 1), torch.randint(-3, 4, s, generator=g)
+        zero = torch.randint(0, 8, s, generator=g) == 0  # exact zeros; a = 0 with b != 0 would make hi = b 2^-10 and
+        a, b = a.masked_fill(zero, 0), b.masked_fill(zero, 0)  # wl zh a multiple of 2^-20: never drawn
+        # (1 - 3 2^-10 lies beyond the tie 1 - 2^-9 of the binade under 1: hi would be 1 - 2^-8 and wl zh a multiple of
+        # 2^-18.  There b takes a's sign.)
+        b = torch.where((a.abs() == 1) & (b == -3 * a), -b, b)
+        return (a + b * 2.0 ** -10).float()
+    ints = lambda *s: torch.randint(-4, 5, s, generator=g).float()
+    T_out = T if T_out is None else T_out
+    o = dict(x=val(B, T, Ci), w=val(Co, Ci, k), b=ints(Co), alpha=alpha, beta=beta, res=None, acc=None, gate=None)
+    if res:
+        o["res"] = ints(B if res_B is None else res_B, (T_out + res_tdiv - 1) // res_tdiv, Co)
+    if acc:
+        o["acc"] = ints(B, T_out, Co)
+    if gate:
+        o["gate"] = torch.tensor([1.0, 2.0, -1.0])[torch.randint(0, 3, (B, Co), generator=g)]
+    gr = 10 + (alpha == 0.5)
+    worst = (K * zscale * (amax + 3 * 2.0 ** -10) ** 2 + 4) * (2 if gate else 1) + (4 if res else 0) + (4 * beta if acc else 0)
+    assert worst * 2.0 ** gr < 2.0 ** 24, (K, worst, gr)
+    assert worst / (2 if gate else 1) < 2.0 ** 13
+    return o
+
+
+def x3_dense_ratio(got, ref_full, terms, K):
+    """a precise conv's fp32 output against ref_full = sum w S in fp64 (fp32 w, the read-out S): the largest |got - ref|
+    / bound, bound = (2^-16 + 2^-17 + 2 (3K + 4) 2^-24) terms -- the dropped wl zl (2^-8 x 2^-8 relative), the weight's
+    lo rounding (2^-17), and dense_ratio's accumulation constants with K -> 3K (as lstm_tf_ref's precise mode).  <= 1."""
+    bound = (2.0 ** -16 + 2.0 ** -17 + 2.0 * (3 * K + 4) * 2.0 ** -24) * terms
+    return ((got.double() - ref_full).abs() / bound.clamp_min(1e-300)).max().item()
+
+
+def x3_staged_ratio(S, s64, mag):
+    """the read-out pair S against the fp64 prologue s of an inexact prologue: the largest |S - s| / (2^-17 |s| + 2^-20
+    mag) -- the split's truncation plus 16 fp32 ulps of the prologue magnitude (pro_ref64's mag) for the fp32 affine and
+    the sine (v_sin_f32 on revolutions in mrfx_conv, libm sinf in conv_x3: the constant is an allowance, not derived)."""
+    return ((S.double() - s64).abs() / (s64.abs() * 2.0 ** -17 + mag * 2.0 ** -20).clamp_min(1e-300)).max().item()
+
+
+def x3_emulate(x, w, b=None, *, sc=None, sh=None, act=None, slope=0.0, snake_alpha=None, pad=0, dil=1, stride=1, res=None,
+               res_tdiv=1, out_scale=1.0, acc_in=None, beta=0.0, gate=None, cscale=1.0, order="seq", mutate=None, ups=0,
+               ups_pad=0, refl=0):
+    """A value-level fp32 model of a precise conv on the CPU: the fp32 prologue (x cscale, sc / sh [B, Ci], LeakyReLU or
+    Snake with torch's fp32 sine), the split, three bf16 products per term accumulated in torch.float32 in the given
+    order -- "seq" tap-major sequential (per term wl zh, wh zl, wh zh), "rev" the same reversed, "blk32" 32-wide K-steps
+    each as wl zh, wh zl, wh zh block sums (the MFMA order of csrc/mrfx.hip) --, then the fp32 epilogue ((acc + b) gate +
+    res) out_scale + beta acc_in.  ups > 0: the polyphase ConvTranspose1d(stride ups, padding ups_pad, k = 2 ups) of
+    weight w.transpose(0, 1), as a conv over the zero-stuffed staged rows with the taps reversed (a zero row adds exact
+    zeros), then ReflectionPad(refl, 0).  -> (y [B, T_out, Co] fp32, S [B, T, Ci] fp32 the staged pair's sum).
+    mutate, one value-only mistake for tests/test_refops_x3.py: "drop_wlzh" (wl zh missing in the second K-step),
+    "lo_tap" (the lo plane of tap 0 taken at tap 1's rows), "lo_row" (staged lo row 3 taken from row 4), "lolo" (wl zl
+    added), "adain_utt0" (utterance 0's AdaIN constants for every utterance), "alpha127" (Snake alpha of channel c & 127),
+    "tdiv" (res_tdiv ignored)."""
+    B, T, Ci = x.shape
+    Co, _, k = w.shape
+    f32 = torch.float32
+    one = torch.ones(B, Ci)
+    sc = one if sc is None else sc.to(f32)
+    sh = 0 * one if sh is None else sh.to(f32)
+    if mutate == "adain_utt0":
+        sc, sh = sc[:1].expand(B, Ci), sh[:1].expand(B, Ci)
+    v = (x.to(f32) * cscale) * sc[:, None, :] + sh[:, None, :]
+    if act == "leaky":
+        v = torch.where(v >= 0, v, v * slope)
+    elif act == "snake":
+        a = snake_alpha.to(f32)
+        if mutate == "alpha127":
+            a = a[torch.arange(Ci) & 127]
+        v = v + torch.sin(a * v) ** 2 / a
+    zh, zl, S = split_ref(v)
+    wh, wl, _ = split_ref(w)
+    if mutate == "lo_row":
+        zl = zl.clone()
+        zl[:, 3] = zl[:, 4]
+    if ups:
+        def stuff(z):
+            u = torch.zeros(B, (T - 1) * ups + 1, Ci)
+            u[:, ::ups] = z
+            return u
+        zh, zl, wh, wl = stuff(zh), stuff(zl), wh.flip(2), wl.flip(2)
+        T, pad, dil, stride = (T - 1) * ups + 1, k - 1 - ups_pad, 1, 1
+    T_out = (T + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    col = lambda z: torch.stack([F.pad(z, (0, 0, pad, pad))[:, j * dil:j * dil + (T_out - 1) * stride + 1:stride]
+                                 for j in range(k)], 2)  # [B, To, k, Ci]
+    ch, cl = col(zh), col(zl)
+    if mutate == "lo_tap":
+        cl = cl.clone()
+        cl[:, :, 0] = cl[:, :, 1]
+    ch, cl = ch.reshape(B, T_out, k * Ci), cl.reshape(B, T_out, k * Ci)
+    mh, ml = (m.permute(0, 2, 1).reshape(Co, k * Ci) for m in (wh, wl))  # [Co, (tap, ci)]
+    acc = torch.zeros(B, T_out, Co, dtype=f32)
+    K = k * Ci
+    if order == "blk32":
+        for s in range(0, K, 32):
+            e = min(s + 32, K)
+            if not (mutate == "drop_wlzh" and s == 32):
+                acc = acc + ch[:, :, s:e] @ ml[:, s:e].t()
+            acc = acc + cl[:, :, s:e] @ mh[:, s:e].t()
+            acc = acc + ch[:, :, s:e] @ mh[:, s:e].t()
+            if mutate == "lolo":
+                acc = acc + cl[:, :, s:e] @ ml[:, s:e].t()
+    else:
+        assert order in ("seq", "rev"), order
+        for i in (range(K) if order == "seq" else range(K - 1, -1, -1)):
+            if not (mutate == "drop_wlzh" and 32 <= i < 64):
+                acc = acc + ch[:, :, i, None] * ml[None, None, :, i]
+            acc = acc + cl[:, :, i, None] * mh[None, None, :, i]
+            acc = acc + ch[:, :, i, None] * mh[None, None, :, i]
+            if mutate == "lolo":
+                acc = acc + cl[:, :, i, None] * ml[None, None, :, i]
+    y = acc
+    if refl:
+        y, T_out = torch.cat([y[:, refl:2 * refl].flip(1), y], 1), T_out + refl
+    if b is not None:
+        y = y + b.to(f32)
+    if gate is not None:
+        y = y * gate.to(f32)[:, None, :]
+    if res is not None:
+        tr = torch.arange(T_out) // (1 if mutate == "tdiv" else res_tdiv)
+        y = y + res.to(f32)[:, tr.clamp_max(res.shape[1] - 1)]
+    y = y * out_scale
+    if acc_in is not None:
+        y = y + beta * acc_in.to(f32)
+    return y, S
+
+
+# kern: conv (mrfx_conv) | narrow (its conv_post form: the waves split the rows) | lin (mrfx_lin) | x3 (csrc/convx.hip
+# conv_x3; ups > 0: its polyphase ConvTranspose, k = 2 ups) | x3flat (its FLAT linear form); tile: the tile height
+# stzs_mrfx_conv_launch gives the case (asserted without a device by tests/test_dispatch_trace.py); pad None: "same"
+PxCase = namedtuple("PxCase", "kern B T Ci Co k dil pro tile cscale stride pad ups refl",
+                    defaults=(1, 1, "none", 128, 1.0, 1, None, 0, 0))
+
+
+def px_id(c):
+    return (f"{c.kern}-{c.B}x{c.T}-{c.Ci}to{c.Co}-k{c.k}d{c.dil}-{c.pro}-t{c.tile}" +
+            (f"-cs{c.cscale}" if c.cscale != 1.0 else "") + (f"-s{c.stride}p{c.pad}" if c.stride != 1 else "") +
+            (f"-ups{c.ups}r{c.refl}" if c.ups else ""))
+
+
+def px_pad(c):
+    return c.dil * (c.k - 1) // 2 if c.pad is None else c.pad
+
+
+def px_T_out(c):
+    """rows of the case's output: the conv's, or T ups + refl for the polyphase ConvTranspose"""
+    return c.T * c.ups + c.refl if c.ups else (c.T + 2 * px_pad(c) - c.dil * (c.k - 1) - 1) // c.stride + 1
+
+
+def precise_probe_cases():
+    """the identity-probe table of tests/test_gpu_precise_probe.py: the smallest cases that reach each code path of
+    csrc/mrfx.hip"""
+    C, out = PxCase, []
+    # single chunk, Snake, 128-row tiles: k3 d8 stages 144 = 16 SB rows exactly, k7 d5 158 of 160; T = 300 gives tile 1
+    # the FULL interior staging path
+    for k, d in ((3, 1), (3, 8), (7, 3), (7, 5), (11, 1)):
+        out += [C("conv", 2, T, 128, 128, k, d, "snake", 128) for T in (5, 128, 129, 300)]
+    for d in (3, 5):  # 64-row tiles (the k11 instantiations are the only reachable ones); T = 200: tile 1 interior
+        out += [C("conv", 2, T, 128, 128, 11, d, "snake", 64) for T in (5, 64, 65, 200)]
+    # multi-chunk (NCH = 0: half-group staging beside live accumulators); 384 -> 176: two output tiles, Co < co_pad
+    for Ci, Co, k, d, tile in ((256, 256, 3, 1, 128), (256, 256, 7, 3, 128), (384, 176, 11, 5, 64)):
+        out += [C("conv", 2, T, Ci, Co, k, d, "snake", tile) for T in (65, 200)]
+    # the AdaIN-block k3 forms (the alpha != 1 template): 130 -> 64 has ci_pad 256 and one valid vector with 2 valid
+    # channels in the second chunk
+    for Ci, Co, pro in ((130, 64, "adain2_leaky8"), (130, 64, "adain_leaky.2"), (130, 64, "adain2"), (130, 64, "none"),
+                        (264, 128, "none")):
+        out += [C("conv", 2, T, Ci, Co, 3, 1, pro, 128) for T in (5, 129)]
+    for pro in ("leaky8", "leaky.01"):  # conv_post: masked stores past Co = 22
+        out += [C("narrow", 2, T, 128, 22, 7, 1, pro, 128) for T in (5, 128, 130)]
+    # mrfx_lin: K 640 = 5 chunks (the next-chunk register prefetch), K 200 (ci_pad 256: whole vectors past Ci); rows
+    # straddling utterances on a non-compact bsx, a partial last tile, T_in = 1; Co 136: 8 valid columns in the second
+    # output tile
+    out += [C("lin", 3, 50, K, 136) for K in (128, 256, 640, 200)]
+    out += [C("lin", B, T, 256, 136) for B, T in ((1, 128), (2, 129), (64, 1))]
+    out += [C("lin", 2, 129, 128, Co) for Co in (8, 600)]
+    out += [C("lin", 3, 50, 200, 136, cscale=0.5)]
+    # conv_x3, fp32 in and out (the only dtype pair the precise engines launch -- tools/dispatch_trace.py --synth): a k5
+    # conv with every prologue instantiation (90 channels: the last vector holds 2), the FLAT k1 form with Ci 48, the
+    # stride-6 k12 noise conv at T = 800 (774 staged rows: the tight row pitch), the polyphase ConvTransposes
+    out += [C("x3", 2, 129, 90, 80, 5, 1, pro) for pro in ("none", "leaky8", "adain2_leaky8", "leaky.1", "snake")]
+    out += [C("x3", 2, 5, 90, 80, 5, 1, "leaky8"), C("x3flat", 3, 50, 48, 136), C("x3flat", 64, 1, 48, 136)]
+    out += [C("x3", 2, 800, 22, 32, 12, 1, pro, stride=6, pad=3) for pro in ("none", "snake")]
+    out += [C("x3", 2, 65, 128, 64, 2 * s, 1, "leaky8", ups=s, refl=r) for s in (6, 10) for r in (0, 1)]
+    out += [C("x3", 2, 65, 128, 64, 12, 1, "leaky.1", ups=6, refl=1)]
+    return out
+
+
+def x3_lds_bytes(rows_in):
+    """csrc/convx.hip x3_lds_bytes restated: two staged tiles at the padded 80-byte row pitch, or at the tight 64-byte
+    pitch where the padded ones would not fit 160 KB, + the 3-slot hi | lo weight ring + the prologue constants"""
+    ring = 3 * 2 * 128 * 32 * 2 + 3 * 32 * 4
+    px = 80 if 2 * ((rows_in * 80 + 15) & ~15) + ring <= 160 * 1024 else 64
+    return max(2 * ((rows_in * px + 15) & ~15) + ring, 128 * 132 * 4 + 2 * 128 * 4 + 2 * 4 * 128 * 2 * 4)
+
+
+def px_expected_launch(c):
+    """what the case must launch: (kernel name, grid x, grid y, dynamic LDS bytes) -- stzs_mrfx_conv_launch restated"""
+    co_pad = (max(c.ups, 1) * c.Co + 127) // 128 * 128
+    if c.kern == "x3flat":
+        return "conv_x3", (c.B * c.T + 127) // 128, co_pad // 128, x3_lds_bytes(128)
+    if c.kern == "x3":  # (the ConvTranspose: two taps over T + 1 rows)
+        To, k = (c.T + 1, 2) if c.ups else (px_T_out(c), c.k)
+        return "conv_x3", c.B * ((To + 127) // 128), co_pad // 128, x3_lds_bytes(127 * c.stride + (k - 1) * c.dil + 1)
+    if c.kern == "lin":
+        return "mrfx_lin", (c.B * c.T + 127) // 128, co_pad // 128, 2 * 128 * 256
+    rows_in = c.tile + (c.k - 1) * c.dil
+    return ("mrfx_conv", c.B * ((c.T + c.tile - 1) // c.tile), 1 if c.kern == "narrow" else co_pad // 128,
+            2 * rows_in * 256 + 2048)
+
+
+def px_make_ops(c, seed=0):
+    """host operands of a case: fp32 x, AdaIN statistics / gamma / beta (distinct per utterance), Snake alpha -- as
+    tests/test_gpu_conv_probe.py make_ops"""
+    adain, act, slope, _ = PX_PRO[c.pro]
+    g = torch.Generator().manual_seed(seed)
+    o = dict(x=torch.randn(c.B, c.T, c.Ci, generator=g), mean=None, alpha=None)
+    if adain == "p2":
+        o["mean"] = torch.zeros(c.B, c.Ci)
+        o["rstd"] = 2.0 ** torch.randint(-2, 3, (c.B, c.Ci), generator=g).float()
+        o["gamma"] = torch.tensor([0.0, 1.0, 3.0, -0.5])[torch.randint(0, 4, (c.B, c.Ci), generator=g)]
+        o["beta"] = torch.zeros(c.B, c.Ci)
+    elif adain == "gen":
+        o["mean"] = torch.randn(c.B, c.Ci, generator=g) * 0.1
+        o["rstd"] = torch.rand(c.B, c.Ci, generator=g) + 0.5
+        o["gamma"] = torch.randn(c.B, c.Ci, generator=g) * 0.2
+        o["beta"] = torch.randn(c.B, c.Ci, generator=g) * 0.2
+    if act == "snake":
+        o["alpha"] = torch.exp(torch.empty(c.Ci).uniform_(math.log(0.25), math.log(4.0), generator=g))
+    return o
+
+
+def px_consts(o):
+    """(sc, sh) fp32 [B, Ci] as the kernel forms them ((1 + gamma) rstd, beta - mean sc, one fp32 rounding each), or
+    (None, None) without AdaIN"""
+    if o["mean"] is None:
+        return None, None
+    sc = (1 + o["gamma"].float()) * o["rstd"].float()
+    return sc, o["beta"].float() - o["mean"].float() * sc
+
+
+def px_layout(c, o, poisoned, dev="cpu"):
+    """device operands of a case.  poisoned: x at channel offset 8 inside a wider (8 more columns) and longer (3 more rows
+    per utterance) buffer of the finite poison 2^100, statistics / gamma-beta rows with non-compact strides; else compact
+    and zero padded.  Every pitch stays a multiple of 8 floats (the launchers refuse anything else)."""
+    Ci = c.Ci
+    xb, xa = guarded((c.B, c.T, Ci), PX_XPADS if poisoned else (0, 0, 0), PX_POISON if poisoned else 0.0, torch.float32, dev)
+    xa.t[:, :, xa.c0:xa.c0 + Ci] = o["x"].to(dev)
+    d = dict(x=xa, xb=xb, pro=None, alpha=o["alpha"].to(dev) if o["alpha"] is not None else None)
+    if o["mean"] is not None:
+        sbs, gbs, boff = (Ci + 24, 2 * Ci + 40, Ci + 16) if poisoned else (Ci, 2 * Ci, Ci)
+        fill = PX_POISON if poisoned else 0.0
+        mean, rstd = (torch.full((c.B, sbs), fill, device=dev) for _ in range(2))
+        gb = torch.full((c.B, gbs), fill, device=dev)
+        mean[:, :Ci], rstd[:, :Ci] = o["mean"].to(dev), o["rstd"].to(dev)
+        gb[:, :Ci], gb[:, boff:boff + Ci] = o["gamma"].to(dev), o["beta"].to(dev)
+        d["pro"] = (mean, rstd, sbs, gb.data_ptr(), gbs, boff)
+        d["keep"] = gb
+    return d
+
+
+def px_y(c, poisoned, dev="cpu", T_out=None):
+    """the fp32 output -> (buffer, Act): NaN-sentinel filled and guarded, or compact zeros"""
+    shp = (c.B, px_T_out(c) if T_out is None else T_out, c.Co)
+    if poisoned:
+        return guarded(shp, PX_YPADS, PX_SENT, torch.float32, dev)
+    return guarded(shp, (0, 0, 0), 0.0, torch.float32, dev)
+
+
+def px_operand(h, dev="cpu"):
+    """a read-only epilogue operand [B, T, Co] in a guarded buffer of its own (finite poison around it; pitches that
+    differ from the output's) -> (buffer, Act)"""
+    buf, a = guarded(tuple(h.shape), (1, 16, 8), PX_POISON, torch.float32, dev)
+    a.t[:, :, a.c0:a.c0 + h.shape[2]] = h.to(dev)
+    return buf, a
+
+
+PX_PACKED = {}
+
+
+def px_pack(c, w, b=None, key=None, dev="cpu"):
+    """pack (and cache, under `key`) w [Co, Ci, k] with its split-operand streams for the case's kernel"""
+    if key is not None and (dev, key) in PX_PACKED:
+        return PX_PACKED[dev, key]
+    from stzs.weights import Arena, pack_conv
+    A = Arena()
+    cw = pack_conv(A, "t", w if c.kern != "lin" else w[:, :, 0], b, ups=c.ups, frag32=c.kern == "conv",
+                   narrow32=c.kern == "narrow", x3=True)
+    A.finalize(dev)
+    cw.w, cw.wx3 = A[cw.w], A[cw.wx3]
+    assert (cw.fx3 is None) == c.kern.startswith("x3"), px_id(c)
+    cw.fx3 = A[cw.fx3] if cw.fx3 is not None else None
+    cw.b = A[cw.b] if cw.b is not None else None
+    cw._arena = A
+    if key is not None:
+        PX_PACKED[dev, key] = cw
+    return cw
+
+
+def px_args(eng, c, cw, d, ya, **epi):
+    """the stzs_conv_args of one launch as the engine fills and routes them (eng.conv(..., collect=[])); the flag the case
+    took is asserted: STZS_CONV_W_FRAG32X3 (csrc/mrfx.hip) for conv / narrow / lin, STZS_CONV_W_X3 (conv_x3) for x3 /
+    x3flat"""
+    from stzs import _lib as L
+    _, act, slope, _ = PX_PRO[c.pro]
+    grp = []
+    geo = dict(ups_pad=c.ups // 2, T_final=c.T * c.ups, refl=c.refl) if c.ups else dict(pad=px_pad(c), dil=c.dil, stride=c.stride)
+    eng.conv(cw, d["x"], ya, pro=d["pro"], pro_act={None: L.ACT_NONE, "leaky": L.ACT_LEAKY, "snake": L.ACT_SNAKE}[act],
+             pro_slope=slope, pro_alpha=d["alpha"], cscale=c.cscale, collect=grp, what=px_id(c), **geo, **epi)
+    a = grp[0]
+    want, other = (L.CONV_W_X3, L.CONV_W_FRAG32X3) if c.kern.startswith("x3") else (L.CONV_W_FRAG32X3, L.CONV_W_X3)
+    assert a.flags & want and not a.flags & other, (px_id(c), a.flags)
+    return a
+
+
+def px_launch(eng, a):
+    """one stzs_conv1d call; its return code is asserted 0"""
+    import ctypes
+    rc = eng.lib.stzs_conv1d(ctypes.byref(a), eng.stream())
+    assert rc == 0, f"stzs_conv1d returned {rc}"
+
+
+def precise_exact_cases():
+    """the exact-sum launches of tests/test_gpu_precise_probe.py (section c): (case, seed, epilogue) with epilogue =
+    dict(res, res_tdiv, res_B, acc, alpha, beta, gate, stat) -- every non-Snake instantiation of mrfx_conv's pick_form
+    and every mrfx_lin<NONE, ...> once"""
+    C, out = PxCase, []
+    E = lambda **kw: dict(dict(res=False, res_tdiv=1, res_B=None, acc=False, alpha=1.0, beta=0.0, gate=False, stat=False), **kw)
+    # the LeakyReLU / identity k3 template, with and without residual, res_tdiv = 2 at odd T; LeakyReLU with slope 2
+    for pro in ("none", "leaky2"):
+        c = C("conv", 2, 129, 130, 64, 3, 1, pro, 128)
+        out += [(c, 11, E(stat=True)), (c, 11, E(res=True, alpha=0.5, stat=True)),
+                (c, 11, E(res=True, res_tdiv=2, alpha=0.5, stat=True))]
+    # large K: 9 chunks, the last with 2 valid channels, two output tiles; |a|, |c| <= 1
+    out.append((C("conv", 2, 129, 1090, 256, 3, 1, "none", 128), 12, E(res=True, res_tdiv=2, alpha=0.5, stat=True)))
+    out.append((C("narrow", 2, 130, 128, 22, 7, 1, "leaky2", 128), 13, E()))  # conv_post shape
+    for gate in (False, True):  # mrfx_lin: gate x residual (rows | the broadcast bsr = 0 form) x accumulate
+        for res in (None, "rows", "bcast"):
+            for acc in (False, True):
+                out.append((C("lin", 3, 50, 256, 136), 14, E(gate=gate, res=res is not None, res_B=1 if res == "bcast" else None,
+                                                              acc=acc, alpha=0.5 if acc else 1.0, beta=2.0 if acc else 0.0)))
+    out.append((C("lin", 2, 129, 640, 136), 15, E(res=True)))  # 5 chunks, a partial last tile
+    # conv_x3: the k5 form with the full epilogue, its LeakyReLU instantiation, the FLAT form with gate + residual, the
+    # stride-6 k12 conv on the tight row pitch
+    out.append((C("x3", 2, 129, 90, 80, 5, 1, "none"), 16, E(res=True, acc=True, alpha=0.5, beta=2.0, stat=True)))
+    out.append((C("x3", 2, 129, 90, 80, 5, 1, "leaky2"), 16, E(stat=True)))
+    out.append((C("x3flat", 3, 50, 48, 136), 17, E(gate=True, res=True)))
+    out.append((C("x3", 2, 800, 22, 32, 12, 1, "none", stride=6, pad=3), 18, E(res=True, alpha=0.5)))
+    # the polyphase ConvTranspose with the reflection row and a residual (the case's w [Co, Ci, k] is the ConvTranspose1d
+    # weight transposed)
+    out.append((C("x3", 2, 65, 128, 64, 12, 1, "leaky2", ups=6, refl=1), 19, E(res=True)))
+    return out
+
+
+def _px_epi_id(e):
+    return (("-res" if e["res"] else "") + (f"-td{e['res_tdiv']}" if e["res_tdiv"] > 1 else "") + ("-bcast" if e["res_B"] else "") +
+            ("-acc" if e["acc"] else "") + (f"-a{e['alpha']:.3g}" if e["alpha"] != 1.0 else "") + ("-gate" if e["gate"] else ""))
+
+
+def px_exact_id(v):
+    c, seed, e = v
+    return px_id(c) + _px_epi_id(e)
+
+
+def px_exact_operands(c, seed, e):
+    """-> (exact_sum_case's dict, the keyword arguments of the case's prologue for x3_emulate / x3_prologue32)"""
+    _, act, slope, exact = PX_PRO[c.pro]
+    assert exact and PX_PRO[c.pro][0] is None
+    ops = exact_sum_case(c.Ci * c.k, seed, B=c.B, T=c.T, Ci=c.Ci, Co=c.Co, k=c.k, T_out=px_T_out(c), alpha=e["alpha"], beta=e["beta"],
+                         res=e["res"], res_tdiv=e["res_tdiv"], res_B=e["res_B"], acc=e["acc"], gate=e["gate"],
+                         zscale=max(slope, 1.0))
+    return ops, dict(act=act, slope=slope)
+
+
+def px_exact_ref(c, ops, pro, e):
+    """the expected output of an exact-sum launch: x3_terms_ref on the real split of the exact prologue value and of the
+    weights -> fp32 [B, T, Co] (asserted to be exactly the fp64 value)"""
+    zh, zl, _ = split_ref(x3_prologue32(ops["x"], None, None, pro["act"], pro["slope"]))
+    wh, wl, _ = split_ref(ops["w"])
+    rr = ops["res"].expand(c.B, -1, -1) if ops["res"] is not None else None
+    geo = dict(pad=px_pad(c), dil=c.dil, stride=c.stride)
+    if c.ups:
+        wh, wl, geo = wh.transpose(0, 1), wl.transpose(0, 1), dict(ups=c.ups, ups_pad=c.ups // 2, refl=c.refl)
+    ref, _ = x3_terms_ref(zh, zl, wh, wl, ops["b"], res=rr, res_tdiv=e["res_tdiv"], out_scale=e["alpha"], acc_in=ops["acc"],
+                          beta=e["beta"], gate=ops["gate"], **geo)
+    assert bool((ref.float().double() == ref).all())
+    return ref.float()
+
+
+def precise_dense_cases():
+    """the random dense launches of section d: (case, epilogue) -- the Snake instantiations (residual x accumulate x alpha
+    on the 128-row single-chunk form, the 64-row k11 d3 form, 256 -> 256, 384 -> 176 on 64-row tiles with Co < co_pad),
+    the LeakyReLU(0.2) block conv behind a general AdaIN, and mrfx_lin with gate + residual + accumulate"""
+    C, out = PxCase, []
+    E = lambda **kw: dict(dict(res=False, res_tdiv=1, res_B=None, acc=False, alpha=1.0, beta=0.0, gate=False, stat=True), **kw)
+    c = C("conv", 2, 300, 128, 128, 7, 3, "snake", 128)
+    out += [(c, E(res=bool(r), acc=bool(a), alpha=1 / 3 if al else 1.0, beta=0.5 if a else 0.0))
+            for r in (0, 1) for a in (0, 1) for al in (0, 1)]
+    out.append((C("conv", 2, 200, 128, 128, 11, 3, "snake", 64), E(res=True, acc=True, alpha=1 / 3, beta=0.5)))
+    out.append((C("conv", 2, 200, 256, 256, 3, 1, "snake", 128), E(res=True, alpha=0.7071)))
+    out.append((C("conv", 2, 200, 384, 176, 11, 5, "snake", 64), E(res=True, alpha=0.7071)))
+    out.append((C("conv", 2, 129, 130, 64, 3, 1, "adain_leaky.2", 128), E(res=True, res_tdiv=2, alpha=0.7071)))
+    out.append((C("lin", 3, 50, 640, 136), E(res=True, acc=True, gate=True, alpha=0.75, beta=1.25, stat=False)))
+    # conv_x3: Snake by libm sinf behind a general AdaIN, the stride-6 conv, the polyphase ConvTranspose with a residual
+    out.append((C("x3", 2, 129, 90, 80, 5, 1, "snake"), E(res=True, acc=True, alpha=1 / 3, beta=0.5)))
+    out.append((C("x3", 2, 800, 22, 32, 12, 1, "snake", stride=6, pad=3), E(res=True, alpha=0.7071)))
+    out.append((C("x3", 2, 65, 128, 64, 12, 1, "leaky.1", ups=6, refl=1), E(res=True, stat=False)))
+    return out
+
+
+def px_dense_id(v):
+    c, e = v
+    return px_id(c) + _px_epi_id(e)
+
+
+def px_dense_operands(c, e):
+    """random fp32 weights, bias and epilogue operands of a dense case -> dict(w, b, res, acc, gate)"""
+    g = torch.Generator().manual_seed(c.Ci + c.k + c.T)
+    wshape, fan = ((c.Ci, c.Co, c.k), 2 * c.Ci) if c.ups else ((c.Co, c.Ci, c.k), c.Ci * c.k)  # (ConvTranspose1d layout)
+    o = dict(w=torch.randn(*wshape, generator=g) / math.sqrt(fan), b=torch.randn(c.Co, generator=g) * 0.1,
+             res=None, acc=None, gate=None)
+    To = px_T_out(c)
+    if e["res"]:
+        o["res"] = torch.randn(c.B, (To + e["res_tdiv"] - 1) // e["res_tdiv"], c.Co, generator=g)
+    if e["acc"]:
+        o["acc"] = torch.randn(c.B, To, c.Co, generator=g)
+    if e["gate"]:
+        o["gate"] = torch.rand(c.B, c.Co, generator=g) + 0.5
+    return o
+
+
+def px_dense_args(eng, c, w, b, o, dev="cpu", *, res=None, res_tdiv=1, acc=None, alpha=1.0, beta=0.0, gate=None, stat=False,
+                  epi_act=None):
+    """the stzs_conv_args of one dense launch on the poisoned layout: res / acc_in in guarded buffers of their own (ldr,
+    lda, bsr, bsa differ from ldy, bsy; a one-utterance res is the broadcast bsr = 0 form), the gate rows at a pitch
+    > Co, and with stat a sentinel-filled statistics slab with stat_ld > Co and one chunk row more than the conv writes
+    -> (args, dict of every buffer: x (d), y (yb, ya), res / acc (ro), gate, slab, nch)"""
+    from stzs.engine import Act
+    d = px_layout(c, o, True, dev)
+    cw = px_pack(c, w, b, None, dev)
+    ro = [px_operand(h, dev) if h is not None else (None, None) for h in (res, acc)]
+    epi = dict(res=ro[0][1], res_tdiv=res_tdiv, acc_in=ro[1][1], alpha=alpha, beta=beta)
+    if res is not None and res.shape[0] == 1 and c.B > 1:
+        epi["res"] = Act(ro[0][1].t[:1], ro[0][1].c0, ro[0][1].C)
+    if epi_act is not None:
+        epi["epi_act"] = epi_act
+    gd = None
+    if gate is not None:
+        gbs = c.Co + 24
+        gd = torch.full((c.B, gbs), PX_POISON, device=dev)
+        gd[:, :c.Co] = gate.to(dev)
+        epi.update(gate=gd.data_ptr(), gate_bs=gbs)
+    yb, ya = px_y(c, True, dev)
+    a = px_args(eng, c, cw, d, ya, **epi)
+    slab, nch = None, (px_T_out(c) + 63) // 64
+    if stat:
+        sld = (c.Co + 7) // 8 * 8 + 8
+        slab = fill_bits((c.B * nch + 1, sld, 2), torch.float32, PX_SENT, dev)  # ([B][nch] rows, then the extra one)
+        a.stat_part, a.stat_ld = slab.data_ptr(), sld
+    return a, dict(d=d, cw=cw, yb=yb, ya=ya, ro=ro, gate=gd, slab=slab, nch=nch)
+
+
+def px_dense_ref(c, S, d, e):
+    """ref_full = sum w S in fp64 (fp32 w, the read-out S) with the case's epilogue, and its terms -> (ref, terms, K)"""
+    geo = dict(ups=c.ups, ups_pad=c.ups // 2, refl=c.refl) if c.ups else dict(pad=px_pad(c), dil=c.dil, stride=c.stride)
+    ref, terms = conv_terms_ref(S, d["w"], d["b"], res=d["res"], res_tdiv=e["res_tdiv"], out_scale=e["alpha"], acc_in=d["acc"],
+                                beta=e["beta"], gate=d["gate"], **geo)
+    return ref, terms, 2 * c.Ci if c.ups else c.Ci * c.k

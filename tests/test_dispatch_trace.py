@@ -111,3 +111,50 @@ def test_linear_probe_cases_launch_what_the_gpu_test_claims(tmp_path):
         else:
             assert nlds <= 16 * 1024, (R.lin_id(c), nlds)  # (static LDS only)
     assert len(lds[64]) == len(lds[128]) == 1 and max(lds[64]) < min(lds[128]) <= LDS_MAX, lds
+
+
+def test_precise_probe_cases_launch_what_the_gpu_test_claims(tmp_path):
+    """every launch of tests/test_gpu_precise_probe.py (refops.precise_probe_cases / precise_exact_cases /
+    precise_dense_cases) through the engine's routing and the real dispatch: each is accepted and launches exactly one
+    kernel of the family it names (mrfx_conv / mrfx_lin / conv_x3), with the grid and the dynamic LDS bytes of
+    refops.px_expected_launch -- 2 rows_in 256 + 2048 tells the 128-row tile from the 64-row tile, the template arguments
+    in the kernel's name the tap count and tile height; conv_x3: refops.x3_lds_bytes tells the padded row pitch from the
+    tight one (the stride-6 conv: 148 608 B), the name the prologue instantiation and the FLAT form.  k7 d5 runs 128-row tiles (158 staged rows, 82 944 B of LDS: one
+    workgroup per CU); the k3 and k7 instantiations of the 64-row form are never launched."""
+    import dispatch_trace as D
+    import refops as R
+    _run(tmp_path, "--precise-cases", "--out", tmp_path / "px.txt")
+    entries = {label: (rc, lines) for _, label, rc, lines in D.parse(tmp_path / "px.txt")}
+    want = {}
+    for c in R.precise_probe_cases():
+        want[f"probe {R.px_id(c)}"] = want[f"probe.compact {R.px_id(c)}"] = c
+    for v in R.precise_exact_cases():
+        want[f"exact {R.px_exact_id(v)}"] = v[0]
+    for v in R.precise_dense_cases():
+        want[f"dense {R.px_dense_id(v)}"] = v[0]
+    assert set(entries) == set(want) and len(want) > 150
+    seen = set()
+    for label, c in want.items():
+        rc, lines = entries[label]
+        launches = [ln.split() for ln in lines if ln.startswith("L ")]
+        assert rc == 0 and len(launches) == 1, (label, rc, lines)
+        name, grid, nlds = launches[0][1], tuple(int(v) for v in launches[0][2:5]), int(launches[0][8])
+        kern, gx, gy, lds = R.px_expected_launch(c)
+        assert kern in name and sum(k in name for k in ("mrfx_lin", "mrfx_conv", "conv_x3")) == 1, (label, name)
+        assert grid == (gx, gy, 1) and nlds == lds <= LDS_MAX, (label, grid, nlds, (gx, gy, lds))
+        if kern == "mrfx_conv":  # mrfx_conv<PACT, HR, HA, KS, BT, NCH, AL, NW>
+            targs = name.split("mrfx_convI")[1].split("EEEv")[0].split("E")
+            ks, bt, nch, nw = int(targs[3][2:]), int(targs[4][2:]), int(targs[5][2:]), targs[7] == "Lb1"
+            assert (ks, bt, nw) == (c.k, c.tile, c.kern == "narrow"), (label, name)
+            assert nch == (1 if c.Ci <= 128 and R.PX_PRO[c.pro][1] == "snake" or nw else 0), (label, name)
+            seen.add((ks, bt))
+        if kern == "conv_x3":  # conv_x3<float, float, PACT, FLAT>
+            targs = name.split("conv_x3I")[1].split("EEEv")[0]
+            pact = {None: 0, "leaky": 1, "snake": 2}[R.PX_PRO[c.pro][1]]
+            assert targs == f"ffLi{pact}ELb{int(c.kern == 'x3flat')}", (label, name)
+            seen.add(("x3", pact, c.kern == "x3flat", nlds))
+    assert {v for v in seen if v[0] != "x3"} == {(3, 128), (7, 128), (11, 128), (11, 64)}, seen
+    assert {v[1:3] for v in seen if v[0] == "x3"} == {(0, False), (1, False), (2, False), (0, True)}, seen
+    assert {v[3] for v in seen if v[0] == "x3"} == {R.x3_lds_bytes(129), R.x3_lds_bytes(774)} == {76800, 148608}
+    k7d5 = R.px_expected_launch(R.PxCase("conv", 2, 300, 128, 128, 7, 5, "snake", 128))
+    assert k7d5[3] == 82944 and 2 * k7d5[3] > LDS_MAX

@@ -162,13 +162,13 @@ def test_conv_x3_kernel(gpu_device, B, T, Ci, Co, k, dil, stride, ups, act):
 
 
 # the precise register-direct conv (csrc/mrfx.hip, STZS_CONV_W_FRAG32X3): B, T, Ci, Co, k, dil, act, residual,
-# accumulate, statistics, res_tdiv -- stage-1 shapes (one 128-channel chunk; 128-row tiles up to a 146-row halo, 64-row
-# tiles beyond: k7 d5, k11 d3 / d5), stage-0 shapes (two chunks), the AdaIN-block k3 forms (LeakyReLU / identity,
+# accumulate, statistics, res_tdiv -- stage-1 shapes (one 128-channel chunk; 128-row tiles up to 16 sb_rows(ks, 128)
+# staged rows -- k7 d5: 158 of 160 --, 64-row tiles beyond: k11 d3 / d5), stage-0 shapes (two chunks), the AdaIN-block k3 forms (LeakyReLU / identity,
 # Ci 1090 = 9 chunks with Ci < ci_pad, x2 shortcut residual), ragged last tiles, Co < co_pad
 MRFX_CASES = [
     (3, 1000, 128, 128, 3, 1, "snake", False, False, True, 1),
     (2, 777, 128, 128, 7, 3, "snake", True, False, True, 1),     # 146-row halo: the largest 128-row tile
-    (2, 1001, 128, 128, 7, 5, "snake", True, True, False, 1),    # 64-row tiles, residual + accumulate
+    (2, 1001, 128, 128, 7, 5, "snake", True, True, False, 1),    # 128-row tiles, 158-row halo; residual + accumulate
     (2, 500, 128, 128, 11, 5, "snake", False, False, True, 1),   # 64-row tiles, 178-row halo -> 114
     (3, 333, 128, 128, 11, 1, "snake", True, True, True, 1),
     (2, 400, 256, 256, 11, 3, "snake", True, False, True, 1),    # stage-0 width: 2 chunks, 64-row tiles

@@ -10,6 +10,7 @@ route every traced call to the same kernels with the same launch geometry: the c
     python tools/dispatch_trace.py --objects OTHER/build --lib /tmp/o.so --sweep --out c.txt     # another build
     python tools/dispatch_trace.py --coverage a.txt b.txt            # registered conv-family kernels never launched
     python tools/dispatch_trace.py --linear-cases --out d.txt        # the identity-probe table of the linears' GPU test
+    python tools/dispatch_trace.py --precise-cases --out e.txt       # every launch of the precise convs' GPU test
 
 Trace lines (hip_record.cpp): "L kernel gx gy gz bx by bz lds", "A kernel attribute value" (hipFuncSetAttribute),
 "C memcpy|memset bytes", "M text" (this driver's markers: "case NAME" before a synthesis case, "call LABEL" / "rc N"
@@ -548,6 +549,52 @@ def linear_cases(lib, out):
     print(f"linear cases: {len(cases)} -> {out}")
 
 
+# ---- mode (d): the precise convs' probe, exact-sum and dense tables ------------------------------------------------
+def precise_cases(lib, out):
+    """every case of tests/refops.py precise_probe_cases() / precise_exact_cases() / precise_dense_cases() (the tables
+    tests/test_gpu_precise_probe.py runs on the device) through the engine's routing and the native dispatch, with the
+    operands the GPU test builds (on the host): one "call <table> <case id>" marker per case, then the launch it made"""
+    import ctypes
+    L = _load(lib, out)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import refops as R
+    from stzs.engine import StyleTTSZS
+    from stzs.params import init_params
+    from stzs.spec import SPEC_TINY
+    eng = StyleTTSZS(SPEC_TINY, init_params(SPEC_TINY, 0), device="cpu")
+    eng.stream = lambda: C.c_void_p(0)  # (no device: the null stream, as tools/launch_trace.py)
+
+    def call(label, a):
+        L.hip_record_mark(f"call {label}".encode())
+        rc = eng.lib.stzs_conv1d(ctypes.byref(a), eng.stream())
+        L.hip_record_mark(f"rc {rc}".encode())
+
+    n = 0
+    for c in R.precise_probe_cases():
+        o = R.px_make_ops(c)
+        for poisoned in (True, False):
+            w = R.delta_weights_T(c.Ci, c.Co, c.k, 0, 0) if c.ups else R.delta_weights(c.Co, c.Ci, c.k, 0, 0)
+            cw = R.px_pack(c, w, None, (c.kern, c.Co, c.Ci, c.k, c.ups))
+            a = R.px_args(eng, c, cw, R.px_layout(c, o, poisoned), R.px_y(c, poisoned)[1])
+            call(f"probe{'' if poisoned else '.compact'} {R.px_id(c)}", a)
+            n += 1
+    for c, seed, e in R.precise_exact_cases():
+        ops, _ = R.px_exact_operands(c, seed, e)
+        w = ops["w"].transpose(0, 1).contiguous() if c.ups else ops["w"]
+        a, keep = R.px_dense_args(eng, c, w, ops["b"], dict(x=ops["x"], mean=None, alpha=None), res=ops["res"],
+                                  res_tdiv=e["res_tdiv"], acc=ops["acc"], alpha=e["alpha"], beta=e["beta"], gate=ops["gate"],
+                                  stat=e["stat"])
+        call(f"exact {R.px_exact_id((c, seed, e))}", a)
+        n += 1
+    for c, e in R.precise_dense_cases():
+        d = R.px_dense_operands(c, e)
+        a, keep = R.px_dense_args(eng, c, d["w"], d["b"], R.px_make_ops(c), res=d["res"], res_tdiv=e["res_tdiv"], acc=d["acc"],
+                                  alpha=e["alpha"], beta=e["beta"], gate=d["gate"], stat=e["stat"])
+        call(f"dense {R.px_dense_id((c, e))}", a)
+        n += 1
+    print(f"precise cases: {n} -> {out}")
+
+
 # ---- coverage -----------------------------------------------------------------------------------------------------
 def registered(objdir, names=CONV_OBJECTS):
     """{object: set of registered kernel names}, from the objects' host stubs (nm)"""
@@ -589,6 +636,7 @@ def main():
     g.add_argument("--sweep", action="store_true")
     g.add_argument("--coverage", nargs="+", metavar="TRACE")
     g.add_argument("--linear-cases", action="store_true")
+    g.add_argument("--precise-cases", action="store_true")
     a = ap.parse_args()
     if a.coverage:
         return coverage(a.objects, a.coverage)
@@ -598,6 +646,8 @@ def main():
         synth(a.synth, lib, out)
     elif a.linear_cases:
         linear_cases(lib, out)
+    elif a.precise_cases:
+        precise_cases(lib, out)
     else:
         sweep(lib, out)
 
