@@ -456,7 +456,11 @@ int stzs_predictor_prep(const stzs_prprep_args* a, void* stream);
 
 /* durations: round(sum_j sigmoid(logit_j)) (serial fp32 sum), clamp >= 1; override if given.
  * lens (optional int32 [B], NULL = none): dur = 0 and dsum = 0 for t >= lens[b] (clamped into [1, T]), whatever
- * override_dur holds there -- the padding tokens of a ragged batch take no frames */
+ * override_dur holds there -- the padding tokens of a ragged batch take no frames.
+ * rate (optional fp32 [B], NULL = the launch as before): row b's speaking rate r_b, dur = max(1, rint(dsum / r_b)) with
+ * the quotient ONE correctly rounded fp32 division (so a host computes the same integer from the same dsum); dsum stays
+ * the raw sum, override_dur and lens win as before.  A rate that is not finite or is <= 0 is taken as 1, the quotient is
+ * held below 2^31: no rate becomes a bad integer */
 typedef struct stzs_dur_args {
     const float* logits;
     const int32_t* override_dur;
@@ -465,6 +469,7 @@ typedef struct stzs_dur_args {
     int64_t ldl, bsl;
     int32_t B, T, nbins, pad_i;
     const int32_t* lens;
+    const float* rate;
 } stzs_dur_args;
 int stzs_durations(const stzs_dur_args* a, void* stream);
 
@@ -736,11 +741,29 @@ int stzs_adaln_expand(const float* mod, const float* table, float* out, int R, i
  * dsig = sigma_{i+1} - sigma_i rounded once from fp64 on the host */
 int stzs_cfg_euler(float* x, const float* D, int B, int N, int cfg, float scale, float s0,
                    float dsig, void* stream);
+/* the same with one guidance scale per row (per-request controls), always on the duplicated state
+ * x [2B, N], D [2B, N]: row b takes Dg = (scales[b] == 1) ? D_c : D_u + scales[b] (D_c - D_u) -- the expression above
+ * unchanged, so row b holds the bits of stzs_cfg_euler on that row alone with scale = scales[b] (cfg = 0 where it is 1);
+ * both halves are updated.  scales fp32 [B] on the device, required (NULL: STZS_EINVAL); B, N <= 0 or s0 <= 0:
+ * STZS_ESHAPE */
+int stzs_cfg_euler_rows(float* x, const float* D, int B, int N, const float* scales, float s0, float dsig,
+                        void* stream);
 /* x[r, :] = eps[b, :] * sigma for both halves (state init) */
 int stzs_state_init(float* x, const float* eps, int B, int N, int cfg, float sigma, void* stream);
 /* y[b, c] = mean_l x[b, l, c0 + c]  (pooled style / prompt vectors), f32 */
 int stzs_mean_rows(const float* x, float* y, int B, int L, int64_t ldx, int64_t bsx, int c0,
                    int C, int64_t ldy, void* stream);
+/* in place: x[b * bs + t * ld] *= mul[b] for t < T, one fp32 multiply per element (the per-row pitch factor on F0,
+ * DESIGN.md §2g); elements between the rows' T are untouched.  16-byte loads and stores where ld == 1 and base and bs
+ * are multiples of 16 bytes (a row's last partial group element-wide), element-wide otherwise.  mul is required (NULL:
+ * STZS_EINVAL, as a base not 4-byte aligned); B, T <= 0, B > 65535, ld < 1 or bs < (T - 1) * ld + 1: STZS_ESHAPE. */
+typedef struct stzs_row_scale_args {
+    float* x;              /* [B, T] f32: element (b, t) at b * bs + t * ld */
+    const float* mul;      /* f32 [B] */
+    int64_t ld, bs;
+    int32_t B, T;
+} stzs_row_scale_args;
+int stzs_row_scale(const stzs_row_scale_args* a, void* stream);
 /* generic strided 2-D copy with dtype conversion: R rows x C cols (row r of batch b).
  * dst_row_off (optional int32 [B], NULL = 0): block b is written dst_row_off[b] rows further down,
  * y[b * bsy + (dst_row_off[b] + r) * ldy + c]; the caller sizes y for the largest offset (a negative one is

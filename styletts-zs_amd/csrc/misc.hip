@@ -2,11 +2,13 @@
 //   stzs_dn_cond      c = silu(pooled prompt + sigma embedding)        (adaLN-single input)
 //   stzs_adaln_expand per-layer modulation = shared + table[l] (+1 on scale chunks)
 //   stzs_cfg_euler    fused classifier-free guidance combine + Euler step, fp32 state
+//   stzs_cfg_euler_rows  the same with one guidance scale per row (per-request controls)
 //   stzs_state_init   x0 = eps * sigma_0 for the (duplicated) CFG state
 //   stzs_mean_rows    pooled style / prompt vectors
 //   stzs_copy2d       strided row copy with dtype conversion (buffer assembly, no torch ops)
 //   stzs_embed        token embedding rows (text front end)
 //   stzs_frame_rows   the ragged decoder's per-stage row counts from the alignment's frame counts
+//   stzs_row_scale    x[b, :] *= mul[b] (the per-row pitch factor on F0)
 #include "common.hpp"
 #include "cfg.hpp"
 
@@ -46,6 +48,42 @@ __global__ void cfg_euler_kernel(float* x, const float* D, int B, int N, int cfg
     const float xn = stzs_cfg_euler_elem(x[i], D[i], cfg ? D[(long)B * N + i] : 0.f, cfg, s, s0, dsig);
     x[i] = xn;
     if (cfg) x[(long)B * N + i] = xn;
+}
+
+// one guidance scale per row, always on the duplicated state: a row whose scale is exactly 1 takes its D_c alone (the
+// cfg = 0 expression on that row), every other row the CFG expression of stzs_cfg_euler_elem unchanged
+__global__ void cfg_euler_rows_kernel(float* x, const float* D, int B, int N, const float* scales, float s0,
+                                      float dsig) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * N) return;
+    const float s = scales[i / N];
+    const float xn = stzs_cfg_euler_elem(x[i], D[i], D[(long)B * N + i], s != 1.f, s, s0, dsig);
+    x[i] = xn;
+    x[(long)B * N + i] = xn;
+}
+
+// x[b, t] *= mul[b], t < T.  WIDE (the host found ld == 1 and base / bs multiples of 16 bytes): 4 elements per thread,
+// a whole group as one 16-byte load and store, the row's last partial group element by element
+template <bool WIDE>
+__global__ __launch_bounds__(256) void row_scale_kernel(const stzs_row_scale_args a) {
+    const int b = blockIdx.y;
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    const float m = a.mul[b];
+    float* X = a.x + (long)b * a.bs;
+    if (WIDE) {
+        const int t0 = v * 4;
+        if (t0 >= a.T) return;
+        if (t0 + 4 <= a.T) {
+            float4 q = *reinterpret_cast<const float4*>(X + t0);
+            q.x *= m, q.y *= m, q.z *= m, q.w *= m;
+            *reinterpret_cast<float4*>(X + t0) = q;
+        } else {
+            for (int t = t0; t < a.T; ++t) X[t] *= m;
+        }
+    } else {
+        if (v >= a.T) return;
+        X[(long)v * a.ld] *= m;
+    }
 }
 
 __global__ void state_init_kernel(float* x, const float* eps, int B, int N, int cfg, float sigma) {
@@ -160,6 +198,24 @@ extern "C" int stzs_cfg_euler(float* x, const float* D, int B, int N, int cfg, f
     if (B <= 0 || N <= 0 || !(s0 > 0.f)) return STZS_ESHAPE;
     return stzs_launch(cfg_euler_kernel, dim3(nblk((long)B * N)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        x, D, B, N, cfg, scale, s0, dsig);
+}
+
+extern "C" int stzs_cfg_euler_rows(float* x, const float* D, int B, int N, const float* scales, float s0, float dsig,
+                                   void* stream) {
+    if (!x || !D || !scales) return STZS_EINVAL;
+    if (B <= 0 || N <= 0 || !(s0 > 0.f)) return STZS_ESHAPE;
+    return stzs_launch(cfg_euler_rows_kernel, dim3(nblk((long)B * N)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), x, D, B, N, scales, s0, dsig);
+}
+
+extern "C" int stzs_row_scale(const stzs_row_scale_args* a, void* stream) {
+    if (!a || !a->x || !a->mul || !stzs_aligned(a->x, 4) || !stzs_aligned(a->mul, 4)) return STZS_EINVAL;
+    if (a->B <= 0 || a->B > 65535 || a->T <= 0 || a->ld < 1 || a->bs < (int64_t)(a->T - 1) * a->ld + 1)
+        return STZS_ESHAPE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool wide = a->ld == 1 && reinterpret_cast<uintptr_t>(a->x) % 16 == 0 && a->bs % 4 == 0;
+    if (wide) return stzs_launch(row_scale_kernel<true>, dim3(nblk((a->T + 3) / 4), a->B), dim3(256), 0, s, *a);
+    return stzs_launch(row_scale_kernel<false>, dim3(nblk(a->T), a->B), dim3(256), 0, s, *a);
 }
 
 extern "C" int stzs_state_init(float* x, const float* eps, int B, int N, int cfg, float sigma, void* stream) {

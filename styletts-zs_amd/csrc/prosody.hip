@@ -57,7 +57,14 @@ __global__ __launch_bounds__(256) void dur_kernel(const stzs_dur_args a) {
     // ragged batch: a padding token (t >= lens[b], clamped into [1, T]) takes no frames, forced or not
     const bool keep = !a.lens || t < min(max(a.lens[b], 1), a.T);
     if (a.dsum) a.dsum[i] = keep ? acc : 0.f;
-    int d = (int)rintf(acc);
+    // per-row speaking rate: ONE correctly rounded division of the sum (the CPU's integer from the same dsum); a rate
+    // that is not finite or not positive is taken as 1, the quotient stays below 2^31 (no bad integer)
+    float q = acc;
+    if (a.rate) {
+        const float r = a.rate[b];
+        q = fminf(__fdiv_rn(acc, (r > 0.f && r <= 3.402823466e38f) ? r : 1.f), 2147483520.f);
+    }
+    int d = (int)rintf(q);
     if (d < 1) d = 1;
     if (a.override_dur) d = a.override_dur[i];
     a.dur[i] = keep ? d : 0;

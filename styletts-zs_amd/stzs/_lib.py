@@ -106,7 +106,8 @@ class PrPrepArgs(C.Structure):
 
 class DurArgs(C.Structure):
     _fields_ = [("logits", vp), ("override_dur", vp), ("dur", vp), ("dsum", vp),
-                ("ldl", i64), ("bsl", i64), ("B", i32), ("T", i32), ("nbins", i32), ("pad_i", i32), ("lens", vp)]
+                ("ldl", i64), ("bsl", i64), ("B", i32), ("T", i32), ("nbins", i32), ("pad_i", i32), ("lens", vp),
+                ("rate", opt_vp)]  # optional fp32 [B]: speaking rate per utterance
 
 
 class AlignArgs(C.Structure):
@@ -189,6 +190,11 @@ class MaskArgs(C.Structure):
     _fields_ = [("x", vp), ("lens", vp), ("ld", i64), ("bs", i64)] + [(n, i32) for n in ("B", "T", "C", "dtype")]
 
 
+class RowScaleArgs(C.Structure):
+    """stzs_row_scale: x[b * bs + t * ld] *= mul[b], t < T"""
+    _fields_ = [("x", vp), ("mul", vp), ("ld", i64), ("bs", i64), ("B", i32), ("T", i32)]
+
+
 class VqArgs(C.Structure):
     _fields_ = [("x", vp), ("codebook", vp), ("idx", vp), ("y", vp), ("ldx", i64), ("ldi", i64), ("ldy", i64)] + \
                [(n, i32) for n in ("R", "G", "K", "dg", "lookup", "pad_i")]
@@ -250,7 +256,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_durations", "stzs_alignment", "stzs_gather_rows", "stzs_adain_dwup", "stzs_f0n_down",
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
            "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_mask_rows", "stzs_code_quantize",
-           "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler",
+           "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler", "stzs_cfg_euler_rows", "stzs_row_scale",
            "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_frame_rows", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
 
@@ -313,6 +319,8 @@ def load():
         "stzs_dn_cond":([vp, vp, vp, i32, i32, vp], i32),
         "stzs_adaln_expand": ([vp, vp, vp, i32, i32, i32, i32, C.c_uint32, vp], i32),
         "stzs_cfg_euler": ([vp, vp, i32, i32, i32, f32, f32, f32, vp], i32),
+        "stzs_cfg_euler_rows": ([vp, vp, i32, i32, vp, f32, f32, vp], i32),
+        "stzs_row_scale": ([P(RowScaleArgs), vp], i32),
         "stzs_state_init": ([vp, vp, i32, i32, i32, f32, vp], i32),
         "stzs_mean_rows": ([vp, vp, i32, i32, i64, i64, i32, i32, i64, vp], i32),
         "stzs_copy2d": ([P(CopyArgs), vp], i32),

@@ -254,6 +254,120 @@ def check_frame_lens(frame_lens, B: int, T40: int) -> list:
     return [int(v) for v in t.tolist()]
 
 
+SPEED_RANGE = (0.25, 4.0)  # speaking rate r_b: a predicted duration becomes max(1, rint(dsum / r_b))
+PITCH_RANGE = (-24.0, 24.0)  # pitch shift p_b in semitones: F0[b, :] *= float32(2 ** (p_b / 12))
+
+
+def check_row_values(v, B: int, name: str, lo=None, hi=None) -> torch.Tensor:
+    """host-side check of one per-request control -> fp32 [B] host tensor.  v: a scalar (broadcast over the rows), a
+    sequence or a host tensor of B numbers, each finite and in [lo, hi] where a bound is given; anything else raises
+    ValueError (as check_text_lens: a device tensor is never read back)."""
+    try:
+        t = torch.as_tensor(v)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{name} must be a number or {B} numbers (one per row): {e}")
+    if t.device.type != "cpu":
+        raise ValueError(f"{name} takes host values")
+    if t.dtype == torch.bool or t.is_complex():
+        raise ValueError(f"{name} must be real numbers, got {t.dtype}")
+    t = t.to(torch.float64)
+    if t.dim() == 0:
+        t = t.expand(B).clone()
+    if t.dim() != 1 or t.shape[0] != B:
+        raise ValueError(f"{name} must be a number or {B} numbers (one per row), got shape {tuple(t.shape)}")
+    if B and not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} must be finite, got {t.tolist()}")
+    if B and ((lo is not None and float(t.min()) < lo) or (hi is not None and float(t.max()) > hi)):
+        raise ValueError(f"{name} must lie in [{lo}, {hi}], got {t.tolist()}")
+    return t.to(torch.float32)
+
+
+def pitch_factors(pitch_shift: torch.Tensor) -> torch.Tensor:
+    """semitones (host fp32 [B]) -> the F0 factors float32(2.0 ** (p / 12)), the power in float64 on the host"""
+    return torch.tensor([2.0 ** (float(p) / 12.0) for p in pitch_shift.tolist()], dtype=torch.float64).to(torch.float32)
+
+
+class RowControls:
+    """per-request controls of one batch of B rows (StyleTTSZS.row_controls makes them): guidance
+    scale, speaking rate and pitch shift, each optional, each one fp32 [B] device array owned by this object and
+    uploaded once.  Row b of a batch run with them computes what the row computes alone with its values as scalars.
+    What a batch launches is fixed when the object is made, from the host values:
+      cfg_scale   absent, or a scalar: the scalar path as before (`cfg_scalar`, a launch argument).  B values: the CFG
+                  form (2B rows, stzs_cfg_euler_rows on `cfg`) when any differs from 1 (`cfg_form`), else the plain form;
+      speed       `rate` goes to the durations kernel when any value differs from 1 (`use_rate`);
+      pitch_shift `mul` = float32(2 ** (p / 12)) multiplies F0 in one stzs_row_scale launch when any value differs from
+                  0 (`use_pitch`).
+    A control that is absent or neutral everywhere adds no launch and no argument: the batch is the one without it.
+    set() rewrites the arrays in place -- same addresses, no allocation -- so a captured graph replays with the new
+    values; a change of what is launched raises ValueError."""
+
+    def __init__(self, B: int, device, cfg_scale=None, speed=None, pitch_shift=None):
+        self.B, self.device = int(B), device
+        if self.B < 1:
+            raise ValueError(f"row_controls: B must be >= 1, got {B}")
+        self.cfg_scalar = None
+        self.cfg = self.rate = self.mul = None
+        self.host = {}
+        cfg, rate, pitch = self._check(cfg_scale, speed, pitch_shift)
+        if cfg_scale is not None and cfg is None:
+            self.cfg_scalar = float(cfg_scale)
+        self.cfg_form = cfg is not None and bool((cfg != 1).any())
+        self.use_rate = rate is not None and bool((rate != 1).any())
+        self.use_pitch = pitch is not None and bool((pitch != 0).any())
+        mk = lambda t: None if t is None else torch.empty(self.B, dtype=torch.float32, device=device)
+        self.cfg, self.rate, self.mul = mk(cfg), mk(rate), mk(pitch)
+        self._upload(cfg, rate, pitch)
+
+    def _check(self, cfg_scale, speed, pitch_shift):
+        """-> (cfg | None, rate | None, pitch | None) host fp32 [B]; a scalar cfg_scale is checked and gives None"""
+        B = self.B
+        cfg = None
+        if cfg_scale is not None:
+            cfg = check_row_values(cfg_scale, B, "cfg_scale", 0.0)
+            if torch.as_tensor(cfg_scale).dim() == 0:
+                cfg = None
+        rate = None if speed is None else check_row_values(speed, B, "speed", *SPEED_RANGE)
+        pitch = None if pitch_shift is None else check_row_values(pitch_shift, B, "pitch_shift", *PITCH_RANGE)
+        return cfg, rate, pitch
+
+    def _upload(self, cfg, rate, pitch):
+        for name, dst, t in (("cfg_scale", self.cfg, cfg), ("speed", self.rate, rate),
+                             ("pitch_shift", self.mul, pitch_factors(pitch) if pitch is not None else None)):
+            if t is not None:
+                dst.copy_(t)
+                self.host[name] = (pitch if name == "pitch_shift" else t).clone()
+
+    def set(self, cfg_scale=None, speed=None, pitch_shift=None):
+        """new values for the controls this object was made with, into the same device arrays (a captured graph that
+        reads them replays with the new values).  ValueError -- before anything is written -- for a value
+        row_controls() would refuse and for a structural change: a control absent when the object was made (or a
+        scalar cfg_scale, a launch argument), the CFG form switching on or off, a rate or a pitch shift that was
+        neutral everywhere (no launch reads its array) becoming active.  An active rate or pitch may go back to
+        neutral: rate 1 and factor 1.0 give the bits of the launch without them."""
+        cfg, rate, pitch = self._check(cfg_scale, speed, pitch_shift)
+        for name, given, dst in (("cfg_scale", cfg_scale, self.cfg), ("speed", speed, self.rate),
+                                 ("pitch_shift", pitch_shift, self.mul)):
+            if given is not None and dst is None:
+                raise ValueError(f"RowControls.set: {name} was not given per row when the controls were made "
+                                 "(structural: make new controls)")
+        if cfg_scale is not None and cfg is None:
+            raise ValueError("RowControls.set: cfg_scale per row cannot become a scalar (structural)")
+        if cfg is not None and bool((cfg != 1).any()) != self.cfg_form:
+            raise ValueError("RowControls.set: the CFG form (any cfg_scale != 1) cannot switch on or off (structural)")
+        if rate is not None and not self.use_rate and bool((rate != 1).any()):
+            raise ValueError("RowControls.set: speed was 1 everywhere when the controls were made (structural)")
+        if pitch is not None and not self.use_pitch and bool((pitch != 0).any()):
+            raise ValueError("RowControls.set: pitch_shift was 0 everywhere when the controls were made (structural)")
+        self._upload(cfg, rate, pitch)
+        return self
+
+    def rows(self, B: int):
+        """these controls for a batch of B rows -> self (ValueError when B is not theirs)"""
+        if int(B) != self.B:
+            raise ValueError(f"controls were made for {self.B} rows, the batch has {B}")
+        return self
+
+
 def sigma_schedule(spec: Spec, steps: int):
     """Distilled pins 1: [smax, 0], 2: [smax, 0.5, 0]; otherwise Karras(rho) + trailing 0 (a1)."""
     if steps == 1:
@@ -402,6 +516,14 @@ class StyleTTSZS:
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.prompt_idx = None  # discrete prompt codes of the last prompt_encode (device int32 [B, L_s, G])
         self.frame_lens = None  # frame counts of the last synth_stream(ragged_frames=True) (device int32 [B])
+
+    def row_controls(self, B: int, cfg_scale=None, speed=None, pitch_shift=None) -> RowControls:
+        """per-request controls for a batch of B rows (RowControls).  Each of cfg_scale (>= 0; 0 is the
+        pure unconditional sample), speed (SPEED_RANGE) and pitch_shift (semitones, PITCH_RANGE) is None, a scalar, a
+        list or a host tensor of B values; wrong shapes, non-finite and out-of-range values raise ValueError.  The
+        values are uploaded once into device arrays the result owns; hand it to sample_style / predict_durations /
+        predict_prosody / prosody_frames / f0n_predictor / synth / synth_stream as controls=."""
+        return RowControls(B, self.device, cfg_scale, speed, pitch_shift)
 
     def check_status(self, reset=True):
         """raise RuntimeError if any LSTM exchange since the last check timed out (its h-states are wrong).
@@ -1123,13 +1245,24 @@ class StyleTTSZS:
 
     # ------------------------------------------------------------------ (a) style diffusion
     def sample_style(self, h_txt: Act, prompt: torch.Tensor, eps: torch.Tensor, steps: int,
-                     cfg_scale: float = 1.0, text_lens=None) -> torch.Tensor:
+                     cfg_scale: float = 1.0, text_lens=None, controls: RowControls = None) -> torch.Tensor:
         """a1-a4: Euler sampling over the distilled / Karras sigma schedule with classifier-free guidance.
         h_txt [B, T, d_txt] bf16, prompt [B, L_s, code] fp32, eps [B, L_s, code] -> codes fp32 [B, L_s, code].
-        text_lens: row b's cross-attention sees its first text_lens[b] text rows, then the prompt (denoiser_prepare)."""
+        text_lens: row b's cross-attention sees its first text_lens[b] text rows, then the prompt (denoiser_prepare).
+        controls: a cfg_scale of theirs replaces the argument -- a scalar as the argument would, B values as one
+        guidance scale per row (the CFG form when any differs from 1: stzs_cfg_euler_rows; a row at exactly 1 takes
+        its conditional prediction alone)."""
         S = self.spec
         B = h_txt.B
-        cfg = cfg_scale != 1.0
+        scales = None
+        if controls is not None:
+            controls.rows(B)
+            if controls.cfg is not None:
+                cfg_scale = 1.0
+                scales = controls.cfg if controls.cfg_form else None
+            elif controls.cfg_scalar is not None:
+                cfg_scale = controls.cfg_scalar
+        cfg = cfg_scale != 1.0 or scales is not None
         R = 2 * B if cfg else B
         sig = sigma_schedule(S, steps)
         if h_txt.t.dtype != self.sdt:  # (the long-form mode: precise fp32 text rows into the bf16 / fp8 sampler)
@@ -1143,6 +1276,10 @@ class StyleTTSZS:
         D = self.act("dn.D", R, S.L_s, S.code_dim, torch.float32)
         for i in range(steps):
             self.denoiser_step(st, i, Act(x), D)
+            if scales is not None:
+                self._raw(self.lib.stzs_cfg_euler_rows, "cfg_euler_rows", x.data_ptr(), D.t.data_ptr(), B, N,
+                          scales.data_ptr(), float(sig[i]), float(sig[i + 1] - sig[i]))
+                continue
             self._raw(self.lib.stzs_cfg_euler, "cfg_euler", x.data_ptr(), D.t.data_ptr(), B, N, int(cfg),
                       float(cfg_scale), float(sig[i]), float(sig[i + 1] - sig[i]))
         return x[:B]
@@ -1343,16 +1480,21 @@ class StyleTTSZS:
 
     # ------------------------------------------------------------------ (b) prosody predictor
     def predict_prosody(self, h_txt: Act, codes: torch.Tensor, durations=None, n_frames=None, text_lens=None,
-                        ragged_frames=False):
+                        ragged_frames=False, controls: RowControls = None):
         """durations: optional int tensor [B, T_txt] (host or device); n_frames: their per-utterance sum if
         known (avoids the device->host sync, e.g. under graph capture).  Returns dict of device tensors.
         text_lens: ragged text rows (duration_encoder); the padding tokens get duration 0 and the alignment never
         references them, so the batch still only has to share its frame count.
         ragged_frames: the rows need not share their frame count: the batch runs at the padded width T40 = the
         longest row's (or n_frames, then the padded width: no host sync at all), each row on its own frames
-        (prosody_frames; the result gains "frame_lens")."""
+        (prosody_frames; the result gains "frame_lens").
+        controls: their speed divides row b's predicted durations (duration_head; forced durations win), so rows of
+        different rates have different frame counts and need ragged_frames; their pitch_shift multiplies F0
+        (f0n_predictor)."""
         if ragged_frames:
             self._check_ragged_frames()
+        if controls is not None:
+            controls.rows(h_txt.B)
         text_lens = self.text_lens(text_lens, h_txt.B, h_txt.T)
         if self.dur_overlap and durations is not None and (n_frames is not None or durations.device.type == "cpu"):
             # the alignment reads the given durations, so the duration LSTM no longer gates the frame branch: it
@@ -1372,11 +1514,11 @@ class StyleTTSZS:
             if text_lens is not None:  # the alignment reads the durations with the padding tokens' zeroed
                 ov = self._mask_durations(ov, text_lens)
             pro = self.prosody_frames(h_txt, codes, d, ov, T40, pair_dur=True, text_lens=text_lens,
-                                      ragged_frames=ragged_frames)
-            du = self.duration_head(d, ov, hd=pro.pop("_hd"), text_lens=text_lens)
+                                      ragged_frames=ragged_frames, controls=controls)
+            du = self.duration_head(d, ov, hd=pro.pop("_hd"), text_lens=text_lens, controls=controls)
             pro.update(du, dur=du["dur"])
             return pro
-        du = self.predict_durations(h_txt, codes, durations, text_lens)
+        du = self.predict_durations(h_txt, codes, durations, text_lens, controls)
         if n_frames is not None:
             T40 = int(n_frames)
         else:
@@ -1387,7 +1529,8 @@ class StyleTTSZS:
             assert ragged_frames or int(tot.min()) == int(tot.max()), \
                 "one batch must share its total frame count (stzs.scheduler.BucketScheduler groups by it)"
             T40 = int(tot.max())
-        return self.prosody_frames(h_txt, codes, du["d"], du["dur"], T40, du, ragged_frames=ragged_frames)
+        return self.prosody_frames(h_txt, codes, du["d"], du["dur"], T40, du, ragged_frames=ragged_frames,
+                                   controls=controls)
 
     def _check_ragged_frames(self):
         """ragged frames run on the default engine's conv forms only: the latency engine's split-K / pair convs and
@@ -1409,13 +1552,15 @@ class StyleTTSZS:
         return dict(asr_buf=Act(asr, 0, S.d_txt + 2), F0=pro["F0"][ix, :2 * T_b].contiguous(),
                     N=pro["N"][ix, :2 * T_b].contiguous(), T40=T_b)
 
-    def predict_durations(self, h_txt: Act, codes: torch.Tensor, durations=None, text_lens=None) -> dict:
+    def predict_durations(self, h_txt: Act, codes: torch.Tensor, durations=None, text_lens=None,
+                          controls: RowControls = None) -> dict:
         """a5-a6: DurationEncoder + duration LSTM + head -> dict(dur int32 [B, T], dsum, logits, d) (device).
         text_lens (ragged batch): dur[b, :text_lens[b]] and d[b, :text_lens[b]] are those of row b alone at
-        T = text_lens[b]; dur is 0 past it (forced or not), d / logits / dsum rows past it are unspecified, finite."""
+        T = text_lens[b]; dur is 0 past it (forced or not), d / logits / dsum rows past it are unspecified, finite.
+        controls: their speed, as duration_head."""
         text_lens = self.text_lens(text_lens, h_txt.B, h_txt.T)
         d, ov = self.duration_encoder(h_txt, codes, durations, text_lens)
-        return self.duration_head(d, ov, text_lens=text_lens)
+        return self.duration_head(d, ov, text_lens=text_lens, controls=controls)
 
     def _mask_durations(self, ov: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
         """given durations with those of the padding tokens (t >= lens[b]) zeroed, in the engine's own buffer
@@ -1474,11 +1619,12 @@ class StyleTTSZS:
                     ov.copy_(durations)
         return xin, ov
 
-    def duration_head(self, d: Act, ov=None, hd: Act = None, text_lens=None) -> dict:
+    def duration_head(self, d: Act, ov=None, hd: Act = None, text_lens=None, controls: RowControls = None) -> dict:
         """a6: duration LSTM + projection + durations kernel (sum of the bin sigmoids, rounded, >= 1; the given
         durations `ov` override it); hd: the duration LSTM's output when already run (lstm_pair)
         -> dict(dur int32 [B, T], dsum, logits, d).  text_lens: the LSTM resets at each row's end, dur and dsum
-        are 0 past it."""
+        are 0 past it.  controls: row b's speed r_b makes a predicted duration max(1, rint(dsum / r_b))
+        (stzs_dur_args.rate); dsum stays the raw sum, given durations and padding tokens are as without it."""
         S, W = self.spec, self.W
         B, T = d.B, d.T
         lens = self.text_lens(text_lens, B, T)
@@ -1494,11 +1640,14 @@ class StyleTTSZS:
             dur.data_ptr(), dsum.data_ptr()
         a.ldl, a.bsl, a.B, a.T, a.nbins = logits.ld, logits.bs, B, T, S.dur_bins
         a.lens = lens.data_ptr() if lens is not None else None
+        if controls is not None and controls.rows(B).use_rate:
+            a.rate = controls.rate.data_ptr()
         self._call(self.lib.stzs_durations, a, "durations")
         return dict(dur=dur, dsum=dsum, logits=logits, d=d)
 
     def prosody_frames(self, h_txt: Act, codes: torch.Tensor, d: Act, dur: torch.Tensor, T40: int,
-                       extra: dict = None, pair_dur=False, text_lens=None, ragged_frames=False) -> dict:
+                       extra: dict = None, pair_dur=False, text_lens=None, ragged_frames=False,
+                       controls: RowControls = None) -> dict:
         """a7-a8 for a batch sharing T40 aligned frames: alignment, gathers, shared LSTM, F0 / N curves.
         pair_dur: the duration LSTM over d runs in the shared LSTM's launch (its output as "_hd"), with the rows'
         text_lens when the text is ragged (the frames are not: one T40).
@@ -1506,7 +1655,8 @@ class StyleTTSZS:
         alignment's total[b], read on the device by every later kernel (no host sync), returned as "frame_lens".
         Row b's idx / en / aligned text rows / F0[b, :2 T_b] / N[b, :2 T_b] are those of the row alone at T40 = T_b;
         past it idx is -1, en and the aligned text rows are zeros, F0 / N finite and unspecified (prosody_rows cuts
-        the rows of one frame count out for decode()).  The default engine only (NotImplementedError otherwise)."""
+        the rows of one frame count out for decode()).  The default engine only (NotImplementedError otherwise).
+        controls: their pitch_shift, as f0n_predictor (dur already holds the rows' rates)."""
         if ragged_frames:
             self._check_ragged_frames()
         S, W = self.spec, self.W
@@ -1529,7 +1679,7 @@ class StyleTTSZS:
         hd = self.act("pr.hd", B, T, S.pr_hid, self.adt) if pair_dur else None
         F0, Nn = self.f0n_predictor(en, codes,
                                     dur_rec=(W.pr_dur_lstm, d, hd, "pr.dur_lstm", text_lens) if pair_dur else None,
-                                    frame_lens=total if ragged_frames else None)
+                                    frame_lens=total if ragged_frames else None, controls=controls)
         out = dict(extra or {}, dur=dur, idx=idx, T40=T40, en=en, asr_buf=enc_in, d=d, F0=F0, N=Nn)
         if ragged_frames:
             out["frame_lens"] = total
@@ -1537,15 +1687,20 @@ class StyleTTSZS:
             out["_hd"] = hd
         return out
 
-    def f0n_predictor(self, en: Act, codes: torch.Tensor, dur_rec=None, frame_lens=None):
+    def f0n_predictor(self, en: Act, codes: torch.Tensor, dur_rec=None, frame_lens=None,
+                      controls: RowControls = None):
         """a8: shared BiLSTM over the aligned frames, then per branch (F0, N) three AdaIN residual blocks (the
         middle one x2 upsampling) and a 1x1 projection.  en [B, T40, pr_in] bf16 -> F0, N fp32 [B, 2 T40].
         frame_lens (int32 [B] device tensor, ragged frames): row b holds frame_lens[b] frames of the T40; the LSTM
         resets at its end, statistics / block convs / upsampling take the lengths (stzs_conv_args.t_lens, ...), so
         F0[b, :2 frame_lens[b]] and N likewise are those of the row alone; past it they are finite, unspecified.
         Statistics are finalised where they are produced (no pro_part, no deferral): the shared xs statistics are
-        complete on the current stream before the F0 || N fork."""
+        complete on the current stream before the F0 || N fork.
+        controls: row b's pitch factor float32(2 ** (p_b / 12)) multiplies F0[b, :] in one stzs_row_scale launch right
+        behind pr.f0_proj (on the F0 branch's stream), before anything reads F0; N is untouched; no launch when the
+        shift is absent or 0 everywhere."""
         fl = frame_lens
+        mul = controls.mul if controls is not None and controls.rows(en.B).use_pitch else None
         if fl is not None:
             self._check_ragged_frames()
         S, W = self.spec, self.W
@@ -1577,6 +1732,8 @@ class StyleTTSZS:
                 ins = {br: ys[br][i] for br in ("f0", "n")}
             for br, out in (("f0", F0), ("n", Nn)):
                 self.conv(W.pr_blk[f"pr.{br}_proj"], ys[br][2], Act(out, 0, 1), what=f"pr.{br}_proj")
+                if br == "f0" and mul is not None:
+                    self.row_scale(out, mul)
             return F0[:, :, 0], Nn[:, :, 0]
 
         def branch(br, out):
@@ -1587,8 +1744,16 @@ class StyleTTSZS:
             self.blk(W.pr_blk[f"pr.{br}1"], y0, y1, ng, gbp, f"pr.{br}1", self.adt, flens=fl)
             self.blk(W.pr_blk[f"pr.{br}2"], y1, y2, ng, gbp, f"pr.{br}2", self.adt, flens=fl, fmul=2)
             self.conv(W.pr_blk[f"pr.{br}_proj"], y2, Act(out, 0, 1), what=f"pr.{br}_proj")
+            if br == "f0" and mul is not None:
+                self.row_scale(out, mul)
         self.fork("f0n", lambda: branch("f0", F0), lambda: branch("n", Nn))
         return F0[:, :, 0], Nn[:, :, 0]
+
+    def row_scale(self, x: torch.Tensor, mul: torch.Tensor):
+        """x [B, T, 1] fp32 (a curve per utterance) *= mul[b], in place: one launch (stzs_row_scale)"""
+        a = L.RowScaleArgs()
+        a.x, a.mul, a.ld, a.bs, a.B, a.T = x.data_ptr(), mul.data_ptr(), x.stride(1), x.stride(0), x.shape[0], x.shape[1]
+        self._call(self.lib.stzs_row_scale, a, "row_scale")
 
     def gather(self, x: Act, idx, y: Act, Cn):
         a = L.GatherArgs()
@@ -2390,7 +2555,8 @@ class StyleTTSZS:
         return torch.cuda.is_current_stream_capturing()
 
     def synth(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None, codes=None,
-              n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None, ragged_frames=False):
+              n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None, ragged_frames=False,
+              controls: RowControls = None):
         """tokens int [B, T_txt]; ref_wav fp32 [B|1, N]; noise fp32 [B, L_s, code]; durations int [B, T_txt]
         (host tensor, or device tensor + n_frames: no device sync); seeds: per-utterance source-noise
         seeds; prompt_idx: teacher-forced discrete prompt codes [B|1, L_s, G] (ref_wav then unused).
@@ -2405,6 +2571,10 @@ class StyleTTSZS:
         in [mel_nfft / 2 + 1, N] -- a ragged reference batch: row b's prompt is computed as alone on
         ref_wav[b, :ref_lens[b]], what lies past it is never read; ignored, as ref_wav is, when
         prompt_idx is given.
+        controls (row_controls()): one guidance scale, speaking rate and pitch shift per row -- row b is
+        computed as alone with its values; a cfg_scale of theirs replaces the argument; rows of different rates have
+        different frame counts (ragged_frames).  Device arrays: a captured synth() replays with what
+        RowControls.set() wrote.
         check: raise RuntimeError if an LSTM exchange of this call timed out (its durations / prosody would be
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
@@ -2412,7 +2582,7 @@ class StyleTTSZS:
         if ragged_frames:
             self._check_ragged_decoder()
         h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                                   n_frames, prompt_idx, text_lens, ref_lens, ragged_frames)
+                                                   n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls)
         wav = self.decode(pro, codes, seeds, frame_lens=pro["frame_lens"] if ragged_frames else None)
         if check and not self._capturing():
             self.check_status()
@@ -2421,7 +2591,7 @@ class StyleTTSZS:
         return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
 
     def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx,
-               text_lens=None, ref_lens=None, ragged_frames=False):
+               text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None):
         """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
         encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
         -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
@@ -2436,13 +2606,13 @@ class StyleTTSZS:
             pe.copy_(prompt.expand(B, -1, -1))
             prompt = pe
         if codes is None:
-            codes = self.sample_style(h, prompt, noise.to(dev, torch.float32), steps, cfg_scale, text_lens)
-        pro = self.predict_prosody(h, codes, durations, n_frames, text_lens, ragged_frames)
+            codes = self.sample_style(h, prompt, noise.to(dev, torch.float32), steps, cfg_scale, text_lens, controls)
+        pro = self.predict_prosody(h, codes, durations, n_frames, text_lens, ragged_frames, controls)
         return h, prompt, codes, pro, list(range(B)) if seeds is None else seeds
 
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
                      codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None,
-                     text_lens=None, ref_lens=None, ragged_frames=False):
+                     text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None):
         """configs[4] long-form synthesis with the streaming iSTFT decoder: the text,
         style, prosody and conv stack run over the whole target (AdaIN instance statistics are
         utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
@@ -2455,12 +2625,13 @@ class StyleTTSZS:
         padded width; the device frame counts (int32 [B]) are in self.frame_lens from the first yield on: row b is
         valid to 600 frame_lens[b] -- the bits of the row's own stream -- and exact zeros from there.  No host sync is
         added, but for the chunked decoder: it reads the frame counts back once (its window schedule is host work)
-        and its chunks tile [0, 600 max frame_lens)."""
+        and its chunks tile [0, 600 max frame_lens).
+        controls: per-row guidance scale, speaking rate and pitch shift, as synth()."""
         if ragged_frames:
             self._check_ragged_decoder()
         S = self.spec
         _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames)
+                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls)
         fl = None
         if ragged_frames:
             fl = self.frame_lens = pro["frame_lens"]

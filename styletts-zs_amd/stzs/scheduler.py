@@ -41,6 +41,12 @@ the requests are sorted by their frame count (known on the host after phase 1; n
 padding) and cut into chunks of <= max_batch; each chunk runs ONE ragged prosody batch and ONE ragged decoder pass on
 its result (the engine's decode(frame_lens=...): row b is computed as alone on its own T_b frames) --
 no per-row copies -- and request i's waveform is the first 600 T40_i samples of its row.
+
+Per-request controls: a Request carries its own guidance scale (None: the scheduler's), speaking rate and
+pitch shift.  They are no part of any grouping key: a phase-1 chunk with a request off the defaults runs with ONE
+RowControls (guidance, rate -- the engine's row_controls), a phase-2 chunk with a shifted request with one for the
+pitch; every row is still computed as alone with its own values.  A chunk of all-default requests makes, call for
+call, the calls from before the controls existed (stats["control_batches"] counts the batches that took controls).
 """
 from __future__ import annotations
 
@@ -61,6 +67,9 @@ class Request:
     noise: torch.Tensor             # fp32 [L_s, code_dim] style noise
     seed: int = 0                   # harmonic-source noise seed
     durations: Optional[torch.Tensor] = None  # optional forced int [T_txt]
+    cfg_scale: Optional[float] = None  # guidance scale (None: the scheduler's)
+    speed: float = 1.0              # speaking rate: predicted durations are divided by it
+    pitch_shift: float = 0.0        # semitones: F0 is multiplied by 2 ** (pitch_shift / 12)
 
 
 class BucketScheduler:
@@ -114,6 +123,27 @@ class BucketScheduler:
             return dec, dec
         return list(self._chunks(list(range(len(frames))))), dec
 
+    def _phase1_controls(self, reqs, ch):
+        """the guidance / rate controls of phase-1 chunk ch -> RowControls, or None when every request of it is at the
+        defaults (the scheduler's guidance scale, rate 1).  A guidance scale the whole chunk shares goes down as a
+        scalar (the engine's scalar path), different ones as one value per row."""
+        cfg = [self.cfg if reqs[i].cfg_scale is None else float(reqs[i].cfg_scale) for i in ch]
+        speed = [float(getattr(reqs[i], "speed", 1.0)) for i in ch]
+        mixed = any(c != cfg[0] for c in cfg)
+        rated = any(r != 1.0 for r in speed)
+        if not mixed and not rated and cfg[0] == self.cfg:
+            return None
+        return self.eng.row_controls(len(ch), cfg_scale=cfg if mixed else cfg[0], speed=speed if rated else None)
+
+    def _phase2_controls(self, per, ch):
+        """the pitch controls of phase-2 chunk ch -> dict(controls=RowControls), or {} when no request of it is
+        shifted (the call then is the one from before the controls)"""
+        pitch = [per[i]["pitch"] for i in ch]
+        if all(p == 0.0 for p in pitch):
+            return {}
+        self._nctl += 1
+        return dict(controls=self.eng.row_controls(len(ch), pitch_shift=pitch))
+
     def _phase2_inputs(self, per, ch):
         """the padded text rows / duration-encoder rows / durations and the codes of requests ch"""
         dev = self.eng.device
@@ -137,7 +167,8 @@ class BucketScheduler:
         for ch in pros:
             h, d, dur, codes = self._phase2_inputs(per, ch)
             Tp = max(per[i]["T40"] for i in ch)
-            pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, Tp, ragged_frames=True)
+            pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, Tp, ragged_frames=True,
+                                     **self._phase2_controls(per, ch))
             fr_n += Tp * len(ch)
             pad_n += Tp * len(ch) - sum(per[i]["T40"] for i in ch)
             # each row's prosody cut out before the next chunk reuses the buffers (data movement only)
@@ -163,7 +194,8 @@ class BucketScheduler:
         for ch in chunks:
             h, d, dur, codes = self._phase2_inputs(per, ch)
             Tp = max(per[i]["T40"] for i in ch)
-            pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, Tp, ragged_frames=True)
+            pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, Tp, ragged_frames=True,
+                                     **self._phase2_controls(per, ch))
             wav = eng.decode(pro, codes, [per[i]["seed"] for i in ch], frame_lens=pro["frame_lens"])
             fr_n += Tp * len(ch)
             pad_n += Tp * len(ch) - sum(per[i]["T40"] for i in ch)
@@ -179,6 +211,7 @@ class BucketScheduler:
         # ragged_ref: without N_ref ----
         per = [None] * len(reqs)
         n1 = 0
+        self._nctl = 0  # batches that ran with controls
         ref_n = pad_n = 0  # reference samples of the phase-1 blocks, and how many of them are padding
         t1 = time.perf_counter()  # (every phase-1 batch ends in a host sync: the wall time is the phase's)
         for forced, ch in self.phase1_groups(reqs):
@@ -209,7 +242,14 @@ class BucketScheduler:
                 ref = torch.stack([reqs[i].ref_wav for i in ch]).to(dev, torch.float32)
             ref_n += Nm * len(ch)
             eps = torch.stack([reqs[i].noise for i in ch]).to(dev, torch.float32)
-            if lens is None and rlens is None:  # (the uniform path, call for call as before)
+            rc = self._phase1_controls(reqs, ch)
+            if rc is not None:
+                self._nctl += 1
+                h = eng.text_encode(tok, lens)
+                prompt = eng.prompt_encode(ref, ref_lens=rlens)
+                codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg, lens, controls=rc)
+                du = eng.predict_durations(h, codes, dur_ov, lens, controls=rc)
+            elif lens is None and rlens is None:  # (the uniform path, call for call as before)
                 h = eng.text_encode(tok)
                 prompt = eng.prompt_encode(ref)
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg)
@@ -224,7 +264,8 @@ class BucketScheduler:
             for j, i in enumerate(ch):
                 T = tl[j]  # the row's own text: what lies past it in a ragged batch is padding
                 per[i] = dict(h=h.t[j, :T].clone(), d=du["d"].t[j, :T].clone(), dur=du["dur"][j, :T].clone(),
-                              codes=codes[j].clone(), T40=int(tot[j]), seed=reqs[i].seed)
+                              codes=codes[j].clone(), T40=int(tot[j]), seed=reqs[i].seed,
+                              pitch=float(getattr(reqs[i], "pitch_shift", 0.0)))
         t1 = time.perf_counter() - t1
         # ---- phase 2: prosody + decoder, grouped by aligned frame count ----
         g2 = OrderedDict()
@@ -250,12 +291,13 @@ class BucketScheduler:
                     T = per[i]["h"].shape[0]
                     h[j, :T], d[j, :T], dur[j, :T] = per[i]["h"], per[i]["d"], per[i]["dur"]
                 codes = torch.stack([per[i]["codes"] for i in ch]).contiguous()
-                pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, T40)
+                pro = eng.prosody_frames(Act(h, 0, S.d_txt), codes, Act(d, 0, S.pr_in), dur, T40,
+                                         **self._phase2_controls(per, ch))
                 wav = eng.decode(pro, codes, [per[i]["seed"] for i in ch])
                 for j, i in enumerate(ch):
                     out[i] = wav[j].clone()
         eng.check_status()  # the phase-2 prosody LSTMs
-        self.stats = dict(requests=len(reqs), phase1_batches=n1, phase2_batches=n2,
+        self.stats = dict(requests=len(reqs), phase1_batches=n1, phase2_batches=n2, control_batches=self._nctl,
                           frame_buckets=sorted(g2.keys()), phase1_ms=1e3 * t1,
                           ref_pad_share=pad_n / max(ref_n, 1),
                           # prosody batches (ragged_frames: fewer than the decoder's; else one per phase-2 batch) and

@@ -12,9 +12,16 @@ around synth() ending in a device synchronise -- and the medians, the phase-1 ba
 reference blocks that is padding go out as one JSON line.
 
     python tools/ragged_traffic.py [--requests 64] [--runs 7] [--warmup 2] [--ref-s LO,HI]
-                                   [--mode both|all|plain|ragged|ragged_ref|ragged_frames|ragged_decoder]
+                                   [--mode both|all|plain|ragged|ragged_ref|ragged_frames|ragged_decoder|controls]
 
 --mode both: plain and ragged (the measurement of "Ragged text batches"); all: the five schedules.
+
+--mode controls: the same 64 requests each draw, seeded, one of four guidance scales (CONTROL_SCALES) and
+a speaking rate uniform in 0.8 .. 1.25.  Two ways to serve them, both with all four ragged flags, timed in alternation:
+`controls`, ONE scheduler with the per-request controls, and `per_scale`, what there was before them -- one scheduler
+per distinct guidance scale on the requests that share it, the rates not expressible (every request at rate 1, so it
+computes other waveforms: the comparison is of batches and wall time).  Batch counts and the medians go out as one
+JSON line.
 """
 import argparse
 import json
@@ -28,6 +35,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "styletts-zs_amd")]
 import torch  # noqa: E402
 
 STEPS, CFG, REF_S, TOK_LO, TOK_HI, SEED = 2, 5.0, 3.0, 20, 200, 2024
+CONTROL_SCALES, RATE_LO, RATE_HI = (1.0, 2.5, 5.0, 7.5), 0.8, 1.25
 
 
 def make_requests(S, n, seed=SEED, ref_s=None):
@@ -45,14 +53,72 @@ def make_requests(S, n, seed=SEED, ref_s=None):
                     noise=torch.randn(S.L_s, S.code_dim, generator=g), seed=k) for k, T in enumerate(lens)]
 
 
+def draw_controls(n, seed=SEED + 2):
+    """-> ([guidance scale], [rate]) of n requests, seeded: a scale of CONTROL_SCALES, a rate in RATE_LO .. RATE_HI"""
+    g = torch.Generator().manual_seed(seed)
+    pick = torch.randint(0, len(CONTROL_SCALES), (n,), generator=g).tolist()
+    rate = (RATE_LO + (RATE_HI - RATE_LO) * torch.rand(n, generator=g, dtype=torch.float64)).tolist()
+    return [CONTROL_SCALES[k] for k in pick], [round(r, 3) for r in rate]
+
+
+def controls_mode(a, eng, S, reqs):
+    """one scheduler with per-request controls against one scheduler per guidance scale -> the result dict"""
+    import copy
+    from stzs.scheduler import BucketScheduler
+    scales, rates = draw_controls(len(reqs))
+    flags = dict(ragged_text=True, ragged_ref=True, ragged_frames=True, ragged_decoder=True)
+    mixed = [copy.copy(r) for r in reqs]
+    for r, s, v in zip(mixed, scales, rates):
+        r.cfg_scale, r.speed = s, v
+    one = BucketScheduler(eng, max_batch=a.max_batch, steps=STEPS, cfg_scale=CFG, **flags)
+    per = {s: (BucketScheduler(eng, max_batch=a.max_batch, steps=STEPS, cfg_scale=s, **flags),
+               [r for r, q in zip(reqs, scales) if q == s]) for s in sorted(set(scales))}
+
+    def run_controls():
+        one.synth(mixed)
+        st = one.stats
+        return st["phase1_batches"], st["phase2_batches"], st["control_batches"]
+
+    def run_per_scale():
+        n1 = n2 = 0
+        for sch, sub in per.values():
+            sch.synth(sub)
+            n1, n2 = n1 + sch.stats["phase1_batches"], n2 + sch.stats["phase2_batches"]
+        return n1, n2, 0
+
+    ways = {"controls": run_controls, "per_scale": run_per_scale}
+    wall, counts = {m: [] for m in ways}, {}
+
+    def timed(m):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        counts[m] = ways[m]()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    for m in ways:
+        for _ in range(a.warmup):
+            timed(m)
+    for _ in range(a.runs):
+        for m in ways:
+            wall[m].append(timed(m))
+    res = dict(mode="controls", requests=len(reqs), steps=STEPS, scales=list(CONTROL_SCALES), rate=[RATE_LO, RATE_HI],
+               requests_per_scale={str(s): len(sub) for s, (_, sub) in per.items()}, runs=a.runs, warmup=a.warmup)
+    for m in ways:
+        res[m] = dict(phase1_batches=counts[m][0], phase2_batches=counts[m][1], control_batches=counts[m][2],
+                      wall_ms_median=round(statistics.median(wall[m]), 2), wall_ms_min=round(min(wall[m]), 2),
+                      wall_ms_max=round(max(wall[m]), 2))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=64)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--max-batch", type=int, default=64)
-    ap.add_argument("--mode", choices=("both", "all", "plain", "ragged", "ragged_ref", "ragged_frames", "ragged_decoder"),
-                    default="both")
+    ap.add_argument("--mode", choices=("both", "all", "plain", "ragged", "ragged_ref", "ragged_frames", "ragged_decoder",
+                                       "controls"), default="both")
     ap.add_argument("--ref-s", default=None, metavar="LO,HI",
                     help="reference lengths seeded uniformly in [LO, HI] seconds (default: 3 s for every request)")
     a = ap.parse_args()
@@ -69,6 +135,9 @@ def main():
         raise SystemExit("ragged_traffic.py measures on the GPU: none is visible")
     eng = StyleTTSZS(S, init_params(S, seed=0), device="cuda:0")
     reqs = make_requests(S, a.requests, ref_s=ref_s)
+    if a.mode == "controls":
+        print(json.dumps(controls_mode(a, eng, S, reqs)))
+        return
     # (ragged_text, ragged_ref, ragged_frames, ragged_decoder)
     modes = {"plain": (False, False, False, False), "ragged": (True, False, False, False),
              "ragged_ref": (True, True, False, False), "ragged_frames": (True, True, True, False),
