@@ -32,7 +32,8 @@ extern "C" {
 #define STZS_EDTYPE (-3)  /* unsupported dtype combination */
 #define STZS_EHIP (-4)    /* HIP runtime error on launch */
 
-enum { STZS_F32 = 0, STZS_BF16 = 1, STZS_I32 = 2, STZS_F8 = 3 /* OCP e4m3fn (gfx950), with a row scale */ };
+enum { STZS_F32 = 0, STZS_BF16 = 1, STZS_I32 = 2, STZS_F8 = 3 /* OCP e4m3fn (gfx950), with a row scale */,
+       STZS_I16 = 4 /* 16-bit PCM: stzs_resample's output only */ };
 enum { STZS_ACT_NONE = 0, STZS_ACT_LEAKY = 1, STZS_ACT_SNAKE = 2, STZS_ACT_GELU = 3, STZS_ACT_SILU = 4 };
 enum { STZS_PRO_NONE = 0, STZS_PRO_ADAIN = 1 };
 /* stzs_conv_args.flags: the caller guarantees that for a ks=1 bf16 linear every input row can be
@@ -764,6 +765,41 @@ typedef struct stzs_row_scale_args {
     int32_t B, T;
 } stzs_row_scale_args;
 int stzs_row_scale(const stzs_row_scale_args* a, void* stream);
+/* ---- sample-rate conversion: a rational polyphase FIR on caller-supplied tables --------------------
+ * With L / M the reduced sr_out / sr_in, output sample j = q L + p (0 <= p < L) of row b is
+ *   y[b, j] = sum_{k < K} h[p, k] * X_b[q M + o[p] + k]
+ * accumulated in fp32 as ONE fmaf chain, k ascending, from +0.0f.  X_b is row b's signal on ABSOLUTE sample indices:
+ * +0.0f below 0 and at or past the row's sample count n_b (such taps still go through the fmaf, so the sign of a zero
+ * result does not depend on tiling or chunking; their memory is never loaded), the row's samples in between.
+ *   n_b = clamp(lens[b] * lens_mul, 0, n_total) in 64 bits (lens NULL: n_total).
+ * x is a WINDOW of the signal: element (b, i) at x[b * bsx + i] is absolute sample x0 + i, i < n_x; a tap inside
+ * [0, n_b) that the window does not hold is read as +0.0f (never out of bounds): the caller passes a window that holds
+ * the taps of [j0, j1) -- stzs/resample.py span() / Resampler.stream do the bookkeeping.
+ * The launch writes the outputs j in [j0, j1) to y[b * bsy + (j - j0)], as fp32 or (STZS_I16) as
+ * clamp(rint(32768 y), -32768, 32767), ties to even.  Outputs at or past out_len_b = ceil(n_b L / M) are exact zeros;
+ * out_lens (optional int32 [B]) receives out_len_b (saturated to int32): the mapped length is a device value.
+ * Tables (device memory; stzs/resample.py design() makes them): h fp32 [L][K4], K4 = K rounded up to a multiple of 4,
+ * the padding columns zero, 16-byte aligned; o int32 [L] with o[p] - floor(p M / L) the same for every p (the taps of
+ * neighbouring outputs advance with the input; a table that breaks this is read at a clamped position, never out of
+ * bounds).  Every output is computed by the same instruction sequence wherever its 1024-output tile starts, so any
+ * split of [j0, j1) and any window give the bits of the whole.
+ * Checked before any HIP call -- STZS_EINVAL: a NULL x / h / o / y, h not 16-byte aligned, x / o / lens / out_lens not
+ * 4-byte aligned, y not aligned to its element, out_dtype neither STZS_F32 nor STZS_I16; STZS_ESHAPE: L, M outside
+ * [1, 1024], K outside [1, 512], M > 8 L, B outside [1, 65535], j0 < 0, j1 < j0, more than 2^31 - 1 tiles, n_x < 0,
+ * n_total < 0, bsx < n_x, bsy < j1 - j0. */
+typedef struct stzs_resample_args {
+    const float* x;         /* [B, n_x] f32 window, row stride bsx */
+    const float* h;         /* f32 [L, K4] */
+    const int32_t* o;       /* int32 [L] */
+    void* y;                /* [B, j1 - j0] f32 or int16, row stride bsy (elements) */
+    const int32_t* lens;    /* optional int32 [B] */
+    int32_t* out_lens;      /* optional int32 [B] output */
+    int64_t x0, n_x, bsx;   /* absolute index of the window's first sample, samples per row, row stride */
+    int64_t n_total;        /* the signal's padded sample count */
+    int64_t j0, j1, bsy;
+    int32_t B, L, M, K, lens_mul, out_dtype;
+} stzs_resample_args;
+int stzs_resample(const stzs_resample_args* a, void* stream);
 /* generic strided 2-D copy with dtype conversion: R rows x C cols (row r of batch b).
  * dst_row_off (optional int32 [B], NULL = 0): block b is written dst_row_off[b] rows further down,
  * y[b * bsy + (dst_row_off[b] + r) * ldy + c]; the caller sizes y for the largest offset (a negative one is

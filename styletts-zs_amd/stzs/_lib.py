@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STZS_LIB", os.path.join(_HERE, "libstzs_hip.so"))
 
 F32, BF16, I32, F8 = 0, 1, 2, 3
+I16 = 4  # 16-bit PCM: stzs_resample's output only
 OK, EINVAL, ESHAPE, EDTYPE, EHIP = 0, -1, -2, -3, -4
 ACT_NONE, ACT_LEAKY, ACT_SNAKE, ACT_GELU, ACT_SILU = 0, 1, 2, 3, 4
 PRO_NONE, PRO_ADAIN = 0, 1
@@ -195,6 +196,13 @@ class RowScaleArgs(C.Structure):
     _fields_ = [("x", vp), ("mul", vp), ("ld", i64), ("bs", i64), ("B", i32), ("T", i32)]
 
 
+class ResampleArgs(C.Structure):
+    """stzs_resample: y[b, j - j0] = sum_k h[p, k] X_b[q M + o[p] + k] for j = q L + p in [j0, j1)"""
+    _fields_ = [("x", vp), ("h", vp), ("o", vp), ("y", vp), ("lens", opt_vp), ("out_lens", opt_vp)] + \
+               [(n, i64) for n in ("x0", "n_x", "bsx", "n_total", "j0", "j1", "bsy")] + \
+               [(n, i32) for n in ("B", "L", "M", "K", "lens_mul", "out_dtype")]
+
+
 class VqArgs(C.Structure):
     _fields_ = [("x", vp), ("codebook", vp), ("idx", vp), ("y", vp), ("ldx", i64), ("ldi", i64), ("ldy", i64)] + \
                [(n, i32) for n in ("R", "G", "K", "dg", "lookup", "pad_i")]
@@ -257,7 +265,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
            "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_mask_rows", "stzs_code_quantize",
            "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler", "stzs_cfg_euler_rows", "stzs_row_scale",
-           "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_frame_rows", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
+           "stzs_resample", "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_frame_rows", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
 
 _lib = None
@@ -321,6 +329,7 @@ def load():
         "stzs_cfg_euler": ([vp, vp, i32, i32, i32, f32, f32, f32, vp], i32),
         "stzs_cfg_euler_rows": ([vp, vp, i32, i32, vp, f32, f32, vp], i32),
         "stzs_row_scale": ([P(RowScaleArgs), vp], i32),
+        "stzs_resample": ([P(ResampleArgs), vp], i32),
         "stzs_state_init": ([vp, vp, i32, i32, i32, f32, vp], i32),
         "stzs_mean_rows": ([vp, vp, i32, i32, i64, i64, i32, i32, i64, vp], i32),
         "stzs_copy2d": ([P(CopyArgs), vp], i32),

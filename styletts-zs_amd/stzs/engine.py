@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import resample as RS
 from .spec import Spec
 from .weights import ConvW, PackedModel
 
@@ -1749,6 +1750,88 @@ class StyleTTSZS:
         self.fork("f0n", lambda: branch("f0", F0), lambda: branch("n", Nn))
         return F0[:, :, 0], Nn[:, :, 0]
 
+    def resample(self, x: torch.Tensor, sr_in: int, sr_out: int, lens=None, lens_mul=1, dtype=torch.float32, out=None,
+                 out_lens=None):
+        """sample-rate conversion on the device, one launch (stzs_resample): x fp32 [B, N] at sr_in ->
+        (y [B, ceil(N L / M)] at sr_out, out_lens int32 [B] on the device).  lens: the rows' own lengths (times
+        lens_mul samples) -- B host integers (checked: each product in [0, N]; uploaded) or an int32 [B] device tensor
+        (trusted: the kernel clamps) -- row b is then the conversion of its first n_b samples alone, exact zeros from
+        out_lens[b] = ceil(n_b L / M) on.  dtype: torch.float32 or torch.int16 (16-bit PCM).  sr_in == sr_out is the
+        identity filter (fp32 -> PCM16).  Bad rates raise ValueError before any launch."""
+        rs = RS.resampler(self.device, sr_in, sr_out)
+        x = x.to(self.device, torch.float32)
+        if lens is not None and not (isinstance(lens, torch.Tensor) and lens.device.type != "cpu"):
+            t = torch.as_tensor(lens)
+            if t.dim() != 1 or t.shape[0] != x.shape[0] or t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f"resample: lens must be {x.shape[0]} integers (one per row)")
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) * int(lens_mul) > x.shape[1]):
+                raise ValueError(f"resample: lens x {lens_mul} must lie in [0, {x.shape[1]}], got {t.tolist()}")
+            lens = t.to(torch.int32).to(self.device)
+        self.launches += 1
+        return rs(x, lens, lens_mul, dtype, out, out_lens)
+
+    def _ref_in(self, ref_wav, ref_sr, ref_lens, prompt_idx):
+        """the reference at the model's rate: with ref_sr another rate, ref_wav [B|1, N] is converted on the device
+        first (one launch, before the encoders fork) and its lengths mapped -- host ref_lens are mapped with out_len,
+        checked at the model's rate as ref_lens() checks them, and uploaded once (at the source rate: the kernel maps
+        them on the device); device ref_lens are trusted and mapped by the kernel, no sync -> (ref_wav, ref_lens)"""
+        S = self.spec
+        if ref_sr is None or int(ref_sr) == S.sr or ref_wav is None or prompt_idx is not None:
+            if ref_sr is not None:
+                RS.ratio(int(ref_sr), S.sr)
+            return ref_wav, ref_lens
+        rs = RS.resampler(self.device, int(ref_sr), S.sr)
+        x = ref_wav.to(self.device, torch.float32)
+        B, N = x.shape
+        n24 = rs.out_len(N)
+        lens = None
+        if ref_lens is not None:
+            if isinstance(ref_lens, torch.Tensor) and ref_lens.device.type != "cpu":
+                if ref_lens.dtype != torch.int32 or tuple(ref_lens.shape) != (B,) or not ref_lens.is_contiguous():
+                    raise ValueError(f"device ref_lens must be a contiguous int32 [{B}] tensor")
+                lens = ref_lens
+            else:
+                host = torch.as_tensor(ref_lens)
+                if host.dim() != 1 or host.shape[0] != B or host.dtype.is_floating_point or host.dtype == torch.bool:
+                    raise ValueError(f"ref_lens must be {B} integers (one per reference row)")
+                if B and (int(host.min()) < 1 or int(host.max()) > N):
+                    raise ValueError(f"ref_lens must lie in [1, {N}] at {ref_sr} Hz, got {host.tolist()}")
+                check_ref_lens([rs.out_len(int(v)) for v in host.tolist()], B, n24, S.mel_nfft)
+                lens = self.buf("rs.ref_lens_in", (B,), torch.int32)
+                lens.copy_(host.to(torch.int32))
+        y = self.buf("rs.ref", (B, n24), torch.float32)
+        ol = self.buf("rs.ref_lens", (B,), torch.int32)
+        self.launches += 1
+        rs(x, lens, 1, torch.float32, y, ol)
+        return y, (None if lens is None else ol)
+
+    def _wav_out(self, wav, out_sr, out_dtype, frame_lens=None):
+        """the decoder's waveform at the caller's rate and type (one launch; None, None: the waveform itself):
+        frame_lens (ragged): row b converted as alone on its 600 frame_lens[b] samples, exact zeros behind"""
+        S = self.spec
+        if out_sr is None and out_dtype is None:
+            return wav
+        sr = S.sr if out_sr is None else int(out_sr)
+        dt = torch.float32 if out_dtype is None else out_dtype
+        rs = RS.resampler(self.device, S.sr, sr)
+        if dt not in (torch.float32, torch.int16):
+            raise ValueError("out_dtype must be torch.float32 or torch.int16")
+        if sr == S.sr and dt == torch.float32:
+            return wav
+        B, N = wav.shape
+        y = self.buf("rs.out", (B, rs.out_len(N)), dt)
+        ol = self.buf("rs.out_lens", (B,), torch.int32)
+        self.launches += 1
+        rs(wav, frame_lens, S.frame40 if frame_lens is not None else 1, dt, y, ol)
+        return y
+
+    def _check_out(self, out_sr, out_dtype):
+        """the output rate and type of synth() / synth_stream(), checked before any launch (ValueError)"""
+        if out_sr is not None:
+            RS.ratio(self.spec.sr, int(out_sr))
+        if out_dtype not in (None, torch.float32, torch.int16):
+            raise ValueError("out_dtype must be torch.float32 or torch.int16")
+
     def row_scale(self, x: torch.Tensor, mul: torch.Tensor):
         """x [B, T, 1] fp32 (a curve per utterance) *= mul[b], in place: one launch (stzs_row_scale)"""
         a = L.RowScaleArgs()
@@ -2556,7 +2639,7 @@ class StyleTTSZS:
 
     def synth(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None, codes=None,
               n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None, ragged_frames=False,
-              controls: RowControls = None):
+              controls: RowControls = None, ref_sr=None, out_sr=None, out_dtype=None):
         """tokens int [B, T_txt]; ref_wav fp32 [B|1, N]; noise fp32 [B, L_s, code]; durations int [B, T_txt]
         (host tensor, or device tensor + n_frames: no device sync); seeds: per-utterance source-noise
         seeds; prompt_idx: teacher-forced discrete prompt codes [B|1, L_s, G] (ref_wav then unused).
@@ -2575,23 +2658,35 @@ class StyleTTSZS:
         computed as alone with its values; a cfg_scale of theirs replaces the argument; rows of different rates have
         different frame counts (ragged_frames).  Device arrays: a captured synth() replays with what
         RowControls.set() wrote.
+        ref_sr: the rate of ref_wav where it is not the model's: converted on the device first (one
+        launch); ref_lens then count samples at ref_sr and are mapped to the model's rate (host: checked there;
+        device: by the kernel, no sync).  out_sr / out_dtype: the waveform converted to that rate and to torch.int16
+        (16-bit PCM) or fp32, one launch behind the decoder: "wav" is at out_sr and the dict gains "sr"; with
+        ragged_frames row b is valid to ceil(600 frame_lens[b] out_sr / sr) and exact zeros from there.  All None: no
+        launch is added.
         check: raise RuntimeError if an LSTM exchange of this call timed out (its durations / prosody would be
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
         -> dict(wav=[B, 600*T40], prompt_idx=[B|1, L_s, G], status=int32 [1], ...)"""
         if ragged_frames:
             self._check_ragged_decoder()
+        self._check_out(out_sr, out_dtype)
         h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                                   n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls)
+                                                   n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls,
+                                                   ref_sr)
         wav = self.decode(pro, codes, seeds, frame_lens=pro["frame_lens"] if ragged_frames else None)
+        wav = self._wav_out(wav, out_sr, out_dtype, pro["frame_lens"] if ragged_frames else None)
         if check and not self._capturing():
             self.check_status()
         if ragged_frames:
             return wav, pro["frame_lens"]
-        return dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
+        out = dict(wav=wav, codes=codes, h_txt=h, prompt=prompt, prompt_idx=self.prompt_idx, status=self.status, **pro)
+        if out_sr is not None or out_dtype is not None:
+            out["sr"] = self.spec.sr if out_sr is None else int(out_sr)
+        return out
 
     def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx,
-               text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None):
+               text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None, ref_sr=None):
         """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
         encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
         -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
@@ -2600,6 +2695,8 @@ class StyleTTSZS:
         tokens = tokens.to(dev, torch.int32) if tokens.device != dev or tokens.dtype != torch.int32 else tokens
         B = tokens.shape[0]
         text_lens = self.text_lens(text_lens, B, tokens.shape[1])  # (host lengths: checked and uploaded once)
+        if ref_sr is not None:  # (a reference at another rate: converted on this stream, before the encoders fork)
+            ref_wav, ref_lens = self._ref_in(ref_wav, ref_sr, ref_lens, prompt_idx)
         h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx, text_lens, ref_lens)
         if prompt.shape[0] == 1 and B > 1:
             pe = self.buf("prompt.bc", (B, S.L_s, S.code_dim), torch.float32)
@@ -2612,7 +2709,8 @@ class StyleTTSZS:
 
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
                      codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None,
-                     text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None):
+                     text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None, ref_sr=None,
+                     out_sr=None, out_dtype=None):
         """configs[4] long-form synthesis with the streaming iSTFT decoder: the text,
         style, prosody and conv stack run over the whole target (AdaIN instance statistics are
         utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
@@ -2626,15 +2724,47 @@ class StyleTTSZS:
         valid to 600 frame_lens[b] -- the bits of the row's own stream -- and exact zeros from there.  No host sync is
         added, but for the chunked decoder: it reads the frame counts back once (its window schedule is host work)
         and its chunks tile [0, 600 max frame_lens).
-        controls: per-row guidance scale, speaking rate and pitch shift, as synth()."""
+        controls: per-row guidance scale, speaking rate and pitch shift, as synth().
+        ref_sr: the reference's rate, as synth().  out_sr / out_dtype: every chunk of either decoder
+        goes through one chunked conversion (Resampler.stream: one launch per chunk, and one for the filter's tail
+        behind the last); the pairs are (first_out_sample, chunk) at out_sr, contiguous, and their concatenation is
+        the bits of the one-shot conversion of the unconverted stream -- with ragged_frames of its rows alone, row b
+        valid to ceil(600 frame_lens[b] out_sr / sr)."""
         if ragged_frames:
             self._check_ragged_decoder()
-        S = self.spec
+        self._check_out(out_sr, out_dtype)
         _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls)
+                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls, ref_sr)
         fl = None
         if ragged_frames:
             fl = self.frame_lens = pro["frame_lens"]
+        chunks = self._stream_chunks(pro, codes, seeds, chunk_s, chunked_halo, fl)
+        if out_sr is not None or out_dtype is not None:
+            chunks = self._convert_chunks(chunks, codes.shape[0], fl, out_sr, out_dtype)
+        yield from chunks
+        if check and not self._capturing():
+            self.check_status()
+
+    def _convert_chunks(self, chunks, B, fl, out_sr, out_dtype):
+        """the (first_sample, chunk) pairs of a streaming decoder through one chunked sample-rate conversion"""
+        S = self.spec
+        rs = RS.resampler(self.device, S.sr, S.sr if out_sr is None else int(out_sr))
+
+        def count():
+            self.launches += 1
+        st = rs.stream(B, fl, S.frame40 if fl is not None else 1, torch.float32 if out_dtype is None else out_dtype,
+                       on_launch=count)
+        for _, c in chunks:
+            j0, y = st.push(c)
+            if y.shape[1]:
+                yield j0, y
+        j0, y = st.push(None, final=True)  # the filter's tail: the outputs whose last taps lie past the signal's end
+        if y.shape[1]:
+            yield j0, y
+
+    def _stream_chunks(self, pro, codes, seeds, chunk_s, chunked_halo, fl):
+        """the (first_sample, chunk) pairs of synth_stream() at the model's rate"""
+        S = self.spec
         if chunked_halo is not None:  # the chunked decoder: chunk-local statistics, first audio after one window
             yield from self.decode_chunked(pro, codes, seeds, max(1, int(round(chunk_s * S.sr / S.frame40))),
                                            int(chunked_halo), **({} if fl is None else dict(frame_lens=fl)))
@@ -2647,8 +2777,6 @@ class StyleTTSZS:
                 rows = self.frame_rows(fl, pro["T40"])
                 post = self.decode(pro, codes, seeds, istft=False, frame_lens=fl, rows=rows)
                 yield from self.istft_stream(post, frames, lens=rows[-1])
-        if check and not self._capturing():
-            self.check_status()
 
 
 # fork sites of the batch-1 latency engine: the text encoder beside the prompt encoder on a forked branch of the

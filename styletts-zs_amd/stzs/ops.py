@@ -21,6 +21,7 @@ operators pin the L1 surface SURVEY §8(b) lists, one per hot-path row of §8(a)
   stzs::mrf_resblock     a12     the MRF of one generator stage (AdaIN + Snake + dilated convs)
   stzs::conv_post_istft  a13     conv_post + exp/sin spectrum + iSTFT
   stzs::code_quantize    (f)1    the discrete style-code quantiser (README.md:5)
+  stzs::resample         §2h     sample-rate conversion, fp32 or 16-bit PCM out (no engine handle)
 
 Model-bound operators take an integer engine handle from `register(engine)` (the packed weights live in
 the engine's device arena).  Every operator is registered for the HIP device ONLY
@@ -461,6 +462,29 @@ def _(handle, z):
     return z.new_empty((z.shape[0], z.shape[1], G), dtype=torch.int32), z.new_empty(z.shape, dtype=torch.float32)
 
 
+# ------------------------------------------------------------------ no engine handle
+@custom_op("stzs::resample", mutates_args=(), device_types="cuda")
+def resample(x: torch.Tensor, sr_in: int, sr_out: int, lens: Optional[torch.Tensor] = None,
+             pcm16: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sample-rate conversion: x fp32 [B, N] at sr_in, lens optional int32 [B] (the rows' sample
+    counts) -> (y [B, ceil(N L / M)] fp32, or int16 PCM with pcm16; out_lens int32 [B]).  No engine handle: the
+    tables of a rate pair are cached per device (stzs/resample.py)."""
+    from .resample import resampler
+    rs = resampler(x.device, sr_in, sr_out)
+    if lens is not None:
+        lens = lens.to(torch.int32).contiguous()
+    return rs(x.float().contiguous(), lens, 1, torch.int16 if pcm16 else torch.float32)
+
+
+@register_fake("stzs::resample")
+def _(x, sr_in, sr_out, lens=None, pcm16=False):
+    from .resample import ratio
+    Lr, Mr = ratio(sr_in, sr_out)
+    n_out = (x.shape[1] * Lr + Mr - 1) // Mr  # (out_len(), kept symbolic for a dynamic N)
+    return (x.new_empty((x.shape[0], n_out), dtype=torch.int16 if pcm16 else torch.float32),
+            x.new_empty((x.shape[0],), dtype=torch.int32))
+
+
 OPS = ["synth", "sample_style", "predict_prosody", "decode", "duration_head", "length_regulate",
        "cfg_euler_step", "istft", "istft_stream", "bilstm", "denoiser_fwd", "f0n_predictor", "decoder_pre",
-       "sine_gen", "conv_transpose_up", "mrf_resblock", "conv_post_istft", "code_quantize"]
+       "sine_gen", "conv_transpose_up", "mrf_resblock", "conv_post_istft", "code_quantize", "resample"]

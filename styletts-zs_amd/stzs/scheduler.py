@@ -47,9 +47,17 @@ pitch shift.  They are no part of any grouping key: a phase-1 chunk with a reque
 RowControls (guidance, rate -- the engine's row_controls), a phase-2 chunk with a shifted request with one for the
 pitch; every row is still computed as alone with its own values.  A chunk of all-default requests makes, call for
 call, the calls from before the controls existed (stats["control_batches"] counts the batches that took controls).
+
+Sample rates: a Request may carry the rate of its reference (ref_sr) and the rate it wants its
+waveform at (out_sr).  Before phase 1 the references of each distinct foreign ref_sr are padded to the longest of them
+and converted in ONE ragged launch (the engine's resample(lens=...): row b the bits of its own conversion); each
+request goes on with its own-length reference at the model's rate, so the grouping keys see those lengths.  After phase
+2 the waveforms of each distinct foreign out_sr are converted the same way.  stats["resample_batches"] counts both; a
+list of requests at the defaults makes, call for call, the calls from before.
 """
 from __future__ import annotations
 
+import dataclasses
 import time
 from collections import OrderedDict
 from dataclasses import dataclass
@@ -57,19 +65,34 @@ from typing import List, Optional
 
 import torch
 
+from . import resample as RS
 from .engine import Act, StyleTTSZS
 
 
 @dataclass
 class Request:
     tokens: torch.Tensor            # int [T_txt]
-    ref_wav: torch.Tensor           # fp32 [N] (24 kHz reference)
+    ref_wav: torch.Tensor           # fp32 [N] reference (at 24 kHz, or at ref_sr)
     noise: torch.Tensor             # fp32 [L_s, code_dim] style noise
     seed: int = 0                   # harmonic-source noise seed
     durations: Optional[torch.Tensor] = None  # optional forced int [T_txt]
     cfg_scale: Optional[float] = None  # guidance scale (None: the scheduler's)
     speed: float = 1.0              # speaking rate: predicted durations are divided by it
     pitch_shift: float = 0.0        # semitones: F0 is multiplied by 2 ** (pitch_shift / 12)
+    ref_sr: Optional[int] = None    # the rate of ref_wav (None: the model's 24 kHz)
+    out_sr: Optional[int] = None    # the rate of the returned waveform (None: the model's)
+
+
+class Stats(dict):
+    """BucketScheduler.stats.  A counter that came with a per-request option and is zero for a list of requests that
+    does not use the option is not listed -- the statistics of such a list are, key for key, the ones from before the
+    option -- and reads as 0."""
+    OPTIONAL = ("resample_batches",)
+
+    def __missing__(self, key):
+        if key in self.OPTIONAL:
+            return 0
+        raise KeyError(key)
 
 
 class BucketScheduler:
@@ -122,6 +145,28 @@ class BucketScheduler:
         if not self.ragged_frames:
             return dec, dec
         return list(self._chunks(list(range(len(frames))))), dec
+
+    def _resample_groups(self, items, sr_of, to_model: bool):
+        """one ragged conversion per distinct foreign rate: items {index: fp32 [n] tensor}, sr_of(index) its other
+        rate -> {index: converted own-length tensor} for the indices at a foreign rate (the others are left out)"""
+        eng, S, dev = self.eng, self.eng.spec, self.eng.device
+        groups = OrderedDict()
+        for i in items:
+            sr = sr_of(i)
+            if sr is not None and int(sr) != S.sr:
+                groups.setdefault(int(sr), []).append(i)
+        done = {}
+        for sr, ids in groups.items():
+            nl = [int(items[i].shape[0]) for i in ids]
+            Nm = max(nl)
+            x = torch.stack([torch.nn.functional.pad(items[i].to(dev, torch.float32), (0, Nm - items[i].shape[0]))
+                             for i in ids])
+            a, b = (sr, S.sr) if to_model else (S.sr, sr)
+            y, _ = eng.resample(x, a, b, lens=nl if min(nl) < Nm else None)
+            self._nrs += 1
+            for j, i in enumerate(ids):
+                done[i] = y[j, :RS.out_len(nl[j], *RS.ratio(a, b))].clone()
+        return done
 
     def _phase1_controls(self, reqs, ch):
         """the guidance / rate controls of phase-1 chunk ch -> RowControls, or None when every request of it is at the
@@ -205,8 +250,17 @@ class BucketScheduler:
         return len(chunks), fr_n, pad_n
 
     def synth(self, reqs: List[Request]) -> List[torch.Tensor]:
-        """-> one fp32 waveform [600 * T40_i] per request, in request order (device tensors)."""
+        """-> one fp32 waveform [600 * T40_i] per request (at its out_sr: [ceil(600 T40_i out_sr / sr)]), in request
+        order (device tensors)."""
         eng, S, dev = self.eng, self.eng.spec, self.eng.device
+        self._nrs = 0  # ragged sample-rate conversions
+        out_srs = [getattr(r, "out_sr", None) for r in reqs]
+        refs = self._resample_groups({i: r.ref_wav for i, r in enumerate(reqs)},
+                                     lambda i: getattr(reqs[i], "ref_sr", None), True)
+        if refs:  # the requests go on with their references at the model's rate (the caller's are left as they are);
+            # the converted ones live on the device, so the others of the list are taken there too: one batch stacks both
+            reqs = [dataclasses.replace(r, ref_wav=refs[i] if i in refs else r.ref_wav.to(dev), ref_sr=None)
+                    for i, r in enumerate(reqs)]
         # ---- phase 1: text / prompt / style / durations, grouped by (T_txt, N_ref) -- ragged_text: without T_txt,
         # ragged_ref: without N_ref ----
         per = [None] * len(reqs)
@@ -297,7 +351,9 @@ class BucketScheduler:
                 for j, i in enumerate(ch):
                     out[i] = wav[j].clone()
         eng.check_status()  # the phase-2 prosody LSTMs
-        self.stats = dict(requests=len(reqs), phase1_batches=n1, phase2_batches=n2, control_batches=self._nctl,
+        for i, w in self._resample_groups({i: w for i, w in enumerate(out)}, lambda i: out_srs[i], False).items():
+            out[i] = w
+        self.stats = Stats(requests=len(reqs), phase1_batches=n1, phase2_batches=n2, control_batches=self._nctl,
                           frame_buckets=sorted(g2.keys()), phase1_ms=1e3 * t1,
                           ref_pad_share=pad_n / max(ref_n, 1),
                           # prosody batches (ragged_frames: fewer than the decoder's; else one per phase-2 batch) and
@@ -306,4 +362,6 @@ class BucketScheduler:
                           # decoder passes, and the share of their padded frame blocks that is tail (ragged_decoder:
                           # the prosody's; else a decoder batch shares its frame count)
                           decoder_batches=n2, decoder_pad_share=fpad_n / max(fr_n, 1) if self.ragged_decoder else 0.0)
+        if self._nrs:  # (the ragged sample-rate conversions, both directions; reads as 0 where it is not listed)
+            self.stats["resample_batches"] = self._nrs
         return out
