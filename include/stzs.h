@@ -145,7 +145,10 @@ typedef struct stzs_conv_args {
      * vector epilogue (Co, ldy, bsy, ldr, bsr, lda, bsa multiples of 8).  Honoured by the generic conv (flags 0 but
      * STZS_CONV_LINEAR_IDS; x and y both bf16 or both fp32; prologue activation NONE or LEAKY) and by the
      * register-direct k3 LeakyReLU / identity form (STZS_CONV_W_FRAG32, ks 3, no acc_in: narrow at 128- and 64-row
-     * tiles, and wide); every other form returns STZS_EINVAL before any HIP call, stzs_conv1d_group likewise.
+     * tiles, and wide); on fp32 rows (in and out) also by the precise forms: the register-direct split-operand form's
+     * k3 LeakyReLU / identity convs (STZS_CONV_W_FRAG32X3, no acc_in) and conv_x3's per-utterance tiles
+     * (STZS_CONV_W_X3, any prologue activation, never its FLAT linear); every other form returns STZS_EINVAL before any
+     * HIP call, stzs_conv1d_group likewise.
      * All of the above is t_lens_rows = 0.
      * t_lens_rows = 1 (the ragged decoder): t_lens[b] is utterance b's OWN row count on this launch's input time
      * axis, T_b = clamp(t_lens[b], 1, T_in); t_lens_mul must be 0 or 1.  The same four rules -- staged rows >= T_b are
@@ -159,7 +162,13 @@ typedef struct stzs_conv_args {
      *    counts INPUT rows, staged input rows q >= T_b are zeros, residual / harmonic-source row loads clamp to the
      *    utterance's own T_b * ups + refl output rows; y rows t < T_b * ups + refl are the utterance's alone;
      *  - the narrow conv (STZS_CONV_W_NARROW32, conv_post): staged rows >= T_b are zeros.
-     * Every other form or combination with t_lens_rows = 1 (the generic conv, LANE16, the precise forms, split-K,
+     * Those three take bf16 input rows only.  On fp32 rows (in and out; bf16 rows are refused) the precise forms:
+     *  - STZS_CONV_W_FRAG32X3: the Snake convs (k 3 / 7 / 11, single- and multi-chunk, 128-row tiles and the 64-row
+     *    tiles of k11 past a 144-row halo'd tile) with the same four epilogue combinations, and the narrow conv_post
+     *    form (Co <= 32, k7, LeakyReLU); its FLAT linear (ks 1) takes no lengths;
+     *  - STZS_CONV_W_X3 (conv_x3, per-utterance tiles): any conv with T_out == T_in, and the polyphase ConvTranspose
+     *    (ups > 0, T_out == T_in + 1) with the rules of the register-direct one.
+     * Every other form or combination with t_lens_rows = 1 (the generic conv, LANE16, conv_f32, split-K,
      * pro_part, a plain linear, t_lens_mul 2, the LeakyReLU / identity block form) and any other value of
      * t_lens_rows returns STZS_EINVAL before any HIP call; stzs_conv1d_group runs problems with lengths one
      * stzs_conv1d at a time (the trio and pair launches stay length-free).  t_lens_rows != 0 with t_lens NULL:

@@ -16,9 +16,11 @@ static inline bool stzs_plain_linear(const stzs_conv_args& a) {
 // `splitk`: whether the form has a split-K variant; `taps`: whether it reads ks / dil / stride (a ROWS linear does not);
 // `t_lens`: whether the form has kernels that honour the ragged frame lengths (stzs_conv_args.t_lens: the generic
 // conv_mfma path without STZS_CONV_A_DMA, and the register-direct form's k3 LeakyReLU / identity block convs --
-// stzs_conv_check holds the rule common to both, each launcher what is particular to its kernels).
+// the precise forms likewise: FRAG32X3's k3 block convs, conv_x3's per-utterance fp32 tiles --
+// stzs_conv_check holds the rule common to all, each launcher what is particular to its kernels).
 // `t_rows`: whether the form has kernels that honour an utterance's own row count (t_lens with t_lens_rows = 1, the
-// ragged decoder: the register-direct form's Snake convs and its polyphase ConvTranspose, the narrow conv_post form).
+// ragged decoder: the register-direct form's Snake convs and its polyphase ConvTranspose, the narrow conv_post form;
+// on fp32 rows the precise forms' Snake / conv_post convs (FRAG32X3) and conv_x3's convs and ConvTranspose).
 // Only the generic path takes prologue statistics from partials (pro_part), and not with STZS_CONV_A_DMA.
 struct stzs_conv_form {
     int bit, excludes;
@@ -27,10 +29,10 @@ struct stzs_conv_form {
 constexpr int STZS_CONV_OLD_FORMS = STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32 | STZS_CONV_W_F32;
 constexpr stzs_conv_form STZS_CONV_FORMS[] = {
     {STZS_CONV_W_FRAG32X3, STZS_CONV_OLD_FORMS | STZS_CONV_W_X3 | STZS_CONV_A_DMA | STZS_CONV_W_FRAG32 | STZS_CONV_ROWS |
-                               STZS_CONV_UPS_NOISE, false, true, false, false},                    // csrc/mrfx.hip
+                               STZS_CONV_UPS_NOISE, false, true, true, true},                      // csrc/mrfx.hip
     {STZS_CONV_W_FRAG32, STZS_CONV_OLD_FORMS | STZS_CONV_A_DMA, false, true, true, true},   // csrc/mrfv.hip, csrc/ups.hip
     {STZS_CONV_ROWS, STZS_CONV_OLD_FORMS | STZS_CONV_W_X3, true, false, false, false},       // csrc/rows.hip
-    {STZS_CONV_W_X3, STZS_CONV_OLD_FORMS, false, true, false, false},                        // csrc/convx.hip conv_x3
+    {STZS_CONV_W_X3, STZS_CONV_OLD_FORMS, false, true, true, true},                          // csrc/convx.hip conv_x3
     {STZS_CONV_W_F32, STZS_CONV_W_LANE16 | STZS_CONV_W_NARROW32, false, true, false, false},       // csrc/convx.hip conv_f32
     {STZS_CONV_W_LANE16, 0, false, true, false, false},                                      // csrc/mrf.hip mrf_conv
     {STZS_CONV_W_NARROW32, 0, false, true, false, true},                                     // csrc/mrf.hip narrow_conv

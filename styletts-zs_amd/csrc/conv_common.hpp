@@ -120,7 +120,10 @@ STZS_DEV float epi_act(float x, float slope) {
 
 // RAG (a ragged frame batch, stzs_conv_args.t_lens; conv_mfma's own instantiations): the residual / accumulate rows
 // clamp into utterance bq's own rows and only stored rows below its count enter the statistics.
-template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int EACT, int BTM, bool RAG = false>
+// RAG == 2 (conv_x3's instantiations, which also run the ragged decoder's polyphase ConvTranspose): the count is clamped
+// into the INPUT rows [1, T_in] (the same value where T_out == T_in) and a ConvTranspose's residual rows clamp into the
+// utterance's own count x ups (+ refl) output rows.
+template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int EACT, int BTM, int RAG = 0>
 STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_bias, const float* c_gate, int bq,
                        int t0, long row0, int tid, int by) {
     const TOut* Rp = reinterpret_cast<const TOut*>(a.res);
@@ -133,8 +136,9 @@ STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_
     const long nrows_flat = (long)a.B * a.T_out;
     const bool small_rows = nrows_flat + BTM < (1L << 22);
     const float invTo = 1.f / (float)a.T_out;
-    const int Tb = RAG ? rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_out) : a.T_out;
-    const long t_hi = ups ? (long)a.T_final + a.refl - 1 : (long)(RAG ? Tb : a.T_out) - 1;
+    const int Tb = RAG == 2 ? rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_in) : RAG ? rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_out) : a.T_out;
+    const long t_hi = ups ? (RAG == 2 ? min((long)a.T_final, (long)Tb * a.ups) : (long)a.T_final) + a.refl - 1
+                          : (long)(RAG ? Tb : a.T_out) - 1;
     const int cv = tid & 15;
     const int n = by * BCO + cv * 8;
     const bool col_ok = n < ncol;
@@ -332,7 +336,7 @@ STZS_DEV void epilogue(const stzs_conv_args& a, const float* ep, const float* c_
     }
 }
 
-template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int BTM, bool RAG = false>
+template <typename TOut, bool FLAT, bool VEC, bool HR, bool HA, int BTM, int RAG = 0>
 STZS_DEV void epilogue_act(const stzs_conv_args& a, const float* ep, const float* c_bias, const float* c_gate, int bq,
                            int t0, long row0, int tid, int by) {
     switch (a.epi_act) {
@@ -349,7 +353,7 @@ STZS_DEV bool splitk_combine_rt(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][
 // 0..15: ONE vectorised variant, HR = bit 0, HA = bit 1, activation index (ep_act) = bits 2-3 (the GEMM kernels:
 // with all twenty variants inlined a gemm_glds instance was ~73 k instructions and its epilogue ran from a cold
 // instruction cache)
-template <typename TOut, bool FLAT, int BTM = BT, int EP = -1, bool RAG = false>
+template <typename TOut, bool FLAT, int BTM = BT, int EP = -1, int RAG = 0>
 STZS_DEV void finish(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][4], unsigned char* smem, int bq, int t0, long row0,
                      int by);
 constexpr int ep_act(int i) { return i == 0 ? STZS_ACT_NONE : (i == 1 ? STZS_ACT_GELU : (i == 2 ? STZS_ACT_SILU : STZS_ACT_LEAKY)); }
@@ -378,7 +382,7 @@ __host__ __device__ inline bool epi_vec(const stzs_conv_args& a) {
 #else
 #define GPROF_E(i)
 #endif
-template <typename TOut, bool FLAT, int BTM, int EP, bool RAG>
+template <typename TOut, bool FLAT, int BTM, int EP, int RAG>
 STZS_DEV void finish(const stzs_conv_args& a, f32x4 (&acc)[BTM / 32][4], unsigned char* smem, int bq, int t0, long row0,
                      int by) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

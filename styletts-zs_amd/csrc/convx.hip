@@ -114,8 +114,17 @@ __host__ __device__ inline int x3_pitch(int rows_in) {
     return 2 * ((rows_in * PX + 15) & ~15) + NSLOT * XSLOT_C + 3 * 32 * 4 <= 160 * 1024 ? PX : PX_TIGHT;
 }
 constexpr int XSLOT = XSLOT_C;
-template <typename TIn, typename TOut, int PACT, bool FLAT>
+// RAG (stzs_conv_args.t_lens, fp32 -> fp32, non-FLAT; instances of their own -- the others compile from the text they
+// had, under the names they had): utterance bq's own row count Tin (clamped into [1, T_in]) bounds the rows that are
+// staged -- rows at or past it are zeros and never loaded -- and finish<..., 2> clamps the residual / accumulate rows and
+// masks the statistics.  The instances with lengths are those whose prologue-activation argument carries X3_RAG
+// (conv_x3<float, float, X3_RAG | act, false>): a further template parameter would rename every existing kernel.
+constexpr int X3_RAG = 8;
+template <typename TIn, typename TOut, int PACTR, bool FLAT>
 __global__ __launch_bounds__(NTHR, 2) void conv_x3(const stzs_conv_args a) {
+    constexpr int PACT = PACTR & (X3_RAG - 1);
+    constexpr bool RAG = (PACTR & X3_RAG) != 0;
+    static_assert(!RAG || !FLAT, "ragged rows: per-utterance tiles");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int ks = FLAT ? 1 : a.ks;
     const int rows_in = (BT - 1) * a.stride + (ks - 1) * a.dil + 1;
@@ -138,6 +147,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_x3(const stzs_conv_args a) {
         bq = blockIdx.x / tpb;
         t0 = (blockIdx.x - bq * tpb) * BT;
     }
+    [[maybe_unused]] int Tin = 0;
+    if constexpr (RAG) Tin = rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_in);  // (uniform per workgroup)
     const int nchunk = a.ci_pad / 32;
     const int NK = nchunk * ks;
     const long stream_el = (long)(a.co_pad / BCO) * NK * (BCO * 32);  // bf16 elements of one (hi | lo) stream
@@ -207,7 +218,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_x3(const stzs_conv_args a) {
                 off = bb * a.bsx + (R - bb * a.T_in) * a.ldx;
             } else {
                 const int tin = t0 * a.stride - a.pad + r;
-                rok = tin >= 0 && tin < a.T_in;
+                if constexpr (RAG) rok = tin >= 0 && tin < Tin;
+                else rok = tin >= 0 && tin < a.T_in;
                 off = (long)tin * a.ldx;
             }
             float o[8];
@@ -269,7 +281,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_x3(const stzs_conv_args a) {
                 }
         }
     }
-    finish<TOut, FLAT, BT>(a, acc, smem, bq, t0, row0, blockIdx.y);
+    if constexpr (RAG) finish<TOut, FLAT, BT, -1, 2>(a, acc, smem, bq, t0, row0, blockIdx.y);
+    else finish<TOut, FLAT, BT>(a, acc, smem, bq, t0, row0, blockIdx.y);
 }
 
 size_t x3_lds_bytes(int rows_in) {
@@ -287,6 +300,13 @@ void (*pick_x3(bool flat, int pro_act))(stzs_conv_args) {
                                        : conv_x3<TI, TO, STZS_ACT_NONE, false>;
 }
 
+// the instance of a launch with lengths (fp32 rows in and out, per-utterance tiles)
+void (*pick_x3_rag(int pro_act))(stzs_conv_args) {
+    return pro_act == STZS_ACT_SNAKE   ? conv_x3<float, float, X3_RAG | STZS_ACT_SNAKE, false>
+           : pro_act == STZS_ACT_LEAKY ? conv_x3<float, float, X3_RAG | STZS_ACT_LEAKY, false>
+                                       : conv_x3<float, float, X3_RAG | STZS_ACT_NONE, false>;
+}
+
 }  // namespace
 
 // internal entries (csrc/conv.hip stzs_conv1d_core, arguments validated there)
@@ -297,7 +317,10 @@ __attribute__((visibility("hidden"))) int stzs_conv_x3_launch(const stzs_conv_ar
     if (lds > 160 * 1024) return STZS_ESHAPE;
     void (*k)(stzs_conv_args) = nullptr;
     const bool flat = stzs_plain_linear(*a) && !a->stat_part;  // (fused statistics: per-utterance tiles only)
-    if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32) k = pick_x3<float, float>(flat, a->pro_act);
+    // lengths (stzs_conv_check: the rule common to every form): fp32 -> fp32, never a FLAT linear
+    if (a->t_lens && (flat || a->in_dtype != STZS_F32 || a->out_dtype != STZS_F32)) return STZS_EINVAL;
+    if (a->t_lens) k = pick_x3_rag(a->pro_act);
+    else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_F32) k = pick_x3<float, float>(flat, a->pro_act);
     else if (a->in_dtype == STZS_F32 && a->out_dtype == STZS_BF16) k = pick_x3<float, bf16_t>(flat, a->pro_act);
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_F32) k = pick_x3<bf16_t, float>(flat, a->pro_act);
     else if (a->in_dtype == STZS_BF16 && a->out_dtype == STZS_BF16) k = pick_x3<bf16_t, bf16_t>(flat, a->pro_act);

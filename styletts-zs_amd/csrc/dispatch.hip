@@ -32,9 +32,11 @@ __attribute__((visibility("hidden"))) int stzs_conv_check(const stzs_conv_args* 
     if (a->t_lens && a->t_lens_rows == 1) {
         // the ragged decoder: t_lens[b] is the utterance's own row count on this launch's input time axis.  A form
         // with such kernels, bf16 rows, stride 1, per-utterance tiles (not a plain linear), no split-K, no pro_part,
-        // no multiplier; row for row, or the polyphase ConvTranspose's T_in + 1 GEMM rows (each launcher: the rest)
+        // no multiplier; row for row, or the polyphase ConvTranspose's T_in + 1 GEMM rows (each launcher: the rest).
+        // The precise forms (FRAG32X3, X3) take fp32 rows and only those
+        const bool x3 = f.bit == STZS_CONV_W_FRAG32X3 || f.bit == STZS_CONV_W_X3;
         if (!f.t_rows || (a->flags & STZS_CONV_A_DMA) || a->stride != 1 || a->splitk > 1 || a->pro_part ||
-            stzs_plain_linear(*a) || a->in_dtype != STZS_BF16 || a->t_lens_mul < 0 || a->t_lens_mul > 1 ||
+            stzs_plain_linear(*a) || a->in_dtype != (x3 ? STZS_F32 : STZS_BF16) || a->t_lens_mul < 0 || a->t_lens_mul > 1 ||
             (a->ups > 0 ? a->T_out != a->T_in + 1 : (a->ups != 0 || a->T_out != a->T_in)) || !stzs_aligned(a->t_lens, 4))
             return STZS_EINVAL;
     } else if (a->t_lens) {

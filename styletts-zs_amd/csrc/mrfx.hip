@@ -66,8 +66,16 @@ STZS_DEV void split8(const float* z, uint4& hi, uint4& lo) {
 // AL: the epilogue scales by a.alpha.  BT: 128 or 64 time rows per tile.
 // NW (narrow, Co <= 32: conv_post 128 -> 22): the 4 waves split the tile's ROWS (32 each) and all compute output
 // channels 0..31 from packed wave 0's fragments; no statistics, masked stores past Co.
-template <int PACT, bool HR, bool HA, int KS, int BT, int NCH, bool AL, bool NW = false>
+// RAG (stzs_conv_args.t_lens; instances of their own -- the k3 LeakyReLU / identity block forms for a ragged frame batch,
+// t_lens_rows 0, the Snake forms and the narrow form for the ragged decoder, t_lens_rows 1; every kernel without the
+// lengths is unchanged): utterance bq's own row count Tin (clamped into [1, T_in]) stands in for T_in in the staging
+// clamp, the zero mask (behind the transform, for every staged row, the dilated halo included: an utterance shorter than
+// the halo stages zeros for all rows past it) and the interior test, and in the epilogue's residual / accumulate-input
+// row clamp and statistics mask.  No workgroup returns early: a 64-row chunk past Tin writes its partial as zeros.
+template <int PACT, bool HR, bool HA, int KS, int BT, int NCH, bool AL, bool NW = false, bool RAG = false>
 __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
+    static_assert(!RAG || NW || PACT == STZS_ACT_SNAKE || (!HA && KS == 3 && BT == 128 && NCH == 0),
+                  "ragged rows: the k3 block convs, the Snake convs, the narrow conv_post form");
     constexpr int MT = NW ? BT / 64 : BT / 16;  // 16-row B fragments per wave
     constexpr int NKC = KS * 4;   // 32-wide K-steps per 128-channel chunk
     constexpr int SB = sb_rows(KS, BT);
@@ -85,6 +93,10 @@ __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
     const int by = lin / nx, bx = lin - by * nx;  // (co tile, utterance x time tile)
     const int bq = bx / tpb;
     const int t0 = (bx - bq * tpb) * BT;
+    // (every use sits behind `if constexpr (RAG)` beside the unchanged expression, so the other instantiations compile
+    // from the text they had)
+    [[maybe_unused]] int Tin = 0;
+    if constexpr (RAG) Tin = rag_rows(a.t_lens, bq, a.t_lens_mul, a.T_in);  // (uniform per workgroup)
     const int nchunk = NCH ? NCH : a.ci_pad >> 7;
     // weights: [co tile][chunk][tap][kq][hl][wave][nt][lane][8] bf16 -> 1024 bf16x8 per K-step
     const bf16x8* Wf = reinterpret_cast<const bf16x8*>(a.w) + ((long)by * nchunk * NKC) * 1024 + (NW ? 0 : wave * 128) +
@@ -148,7 +160,8 @@ __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
                     for (int i = 0; i < G; ++i) {  // 32-bit offsets from the utterance base (SGPR)
                         if (i0 + i >= SB) break;
                         int tin = t0 - a.pad + rsub + 16 * (i0 + i);
-                        if constexpr (!FULL) tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
+                        if constexpr (!FULL && RAG) tin = tin < 0 ? 0 : (tin >= Tin ? Tin - 1 : tin);
+                        else if constexpr (!FULL) tin = tin < 0 ? 0 : (tin >= a.T_in ? a.T_in - 1 : tin);
                         const unsigned off = (unsigned)(tin * (int)a.ldx + cl) * 4u;
                         const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + off);
                         raw[i][0] = p[0];
@@ -190,7 +203,9 @@ __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
                     }
                     if constexpr (!FULL) {  // zero padding / channels past Ci
                         const int tin = t0 - a.pad + r;
-                        const bool ok = c_ok && tin >= 0 && tin < a.T_in;
+                        bool ok;
+                        if constexpr (RAG) ok = c_ok && tin >= 0 && tin < Tin;
+                        else ok = c_ok && tin >= 0 && tin < a.T_in;
 #pragma unroll
                         for (int j = 0; j < 8; ++j) z[j] = ok ? z[j] : 0.f;
                     }
@@ -203,7 +218,9 @@ __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
                     }
                 }
             };
-            const bool interior = t0 - a.pad >= 0 && t0 - a.pad + 16 * SB <= a.T_in && cc * 128 + 128 <= a.Ci;
+            bool interior;
+            if constexpr (RAG) interior = t0 - a.pad >= 0 && t0 - a.pad + 16 * SB <= Tin && cc * 128 + 128 <= a.Ci;
+            else interior = t0 - a.pad >= 0 && t0 - a.pad + 16 * SB <= a.T_in && cc * 128 + 128 <= a.Ci;
             if (interior)
                 stage(std::integral_constant<bool, true>{});
             else
@@ -299,7 +316,9 @@ __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
 #pragma unroll
         for (int m = 0; m < MH; ++m) {
             const int t = t0 + wrow + (h * MH + m) * 16 + n;
-            const int tc = t < a.T_out ? t : a.T_out - 1;
+            int tc;
+            if constexpr (RAG) tc = t < Tin ? t : Tin - 1;  // (T_out == T_in: no residual row at or past Tin is read)
+            else tc = t < a.T_out ? t : a.T_out - 1;
             if constexpr (HR) {
                 const int tr = TD1 ? tc : tc / a.res_tdiv;
                 const float4* p = reinterpret_cast<const float4*>(Rq + (long)tr * a.ldr + coc);
@@ -352,7 +371,10 @@ __global__ __launch_bounds__(NTH, 2) void mrfx_conv(const stzs_conv_args a) {
                         if (i < ncv) Y[(long)t * a.ldy + coc + i] = v[i];
                 }
             }
-            if (stat && ok) {
+            bool st_ok;
+            if constexpr (RAG) st_ok = stat && ok && t < Tin;
+            else st_ok = stat && ok;
+            if (st_ok) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     ss[i] += v[i];
@@ -612,6 +634,43 @@ void (*pick_form(const stzs_conv_args& a))(stzs_conv_args) {
     return nullptr;
 }
 
+// the instances of a launch with lengths (RAG).  Mode 0 (a ragged frame batch): the four k3 block forms of pick_form.
+// Mode 1 (the ragged decoder): the Snake forms at every (ks, BT) the launcher picks -- 128-row tiles, 64-row tiles for
+// k11 past a 144-row halo'd tile -- single- and multi-chunk, with the generator's four epilogue combinations as
+// csrc/mrfv_kernel.hpp pick_rag enumerates them (an accumulate input or alpha != 1 without a residual: nullptr).
+template <bool HR, bool HA, bool AL, int NCH>
+void (*pick_rag_ks(int ks, int bt))(stzs_conv_args) {
+    if (bt == 64) return ks == 11 ? mrfx_conv<STZS_ACT_SNAKE, HR, HA, 11, 64, NCH, AL, false, true> : nullptr;
+    switch (ks) {
+        case 3: return mrfx_conv<STZS_ACT_SNAKE, HR, HA, 3, 128, NCH, AL, false, true>;
+        case 7: return mrfx_conv<STZS_ACT_SNAKE, HR, HA, 7, 128, NCH, AL, false, true>;
+        case 11: return mrfx_conv<STZS_ACT_SNAKE, HR, HA, 11, 128, NCH, AL, false, true>;
+        default: return nullptr;
+    }
+}
+template <int NCH>
+void (*pick_rag(int ks, int bt, bool hr, bool ha, bool al))(stzs_conv_args) {
+    if (!hr) return (ha || al) ? nullptr : pick_rag_ks<false, false, false, NCH>(ks, bt);
+    if (ha) return pick_rag_ks<true, true, true, NCH>(ks, bt);
+    return al ? pick_rag_ks<true, false, true, NCH>(ks, bt) : pick_rag_ks<true, false, false, NCH>(ks, bt);
+}
+void (*pick_rag_form(const stzs_conv_args& a, int bt))(stzs_conv_args) {
+    const bool R = a.res != nullptr, A = a.acc_in != nullptr;
+    if (a.t_lens_rows == 1) {
+        if (a.pro_act != STZS_ACT_SNAKE) return nullptr;
+        const bool al = a.alpha != 1.f;
+        return a.ci_pad == 128 ? pick_rag<1>(a.ks, bt, R, A, al) : pick_rag<0>(a.ks, bt, R, A, al);
+    }
+    if (A || a.ks != 3 || bt != 128) return nullptr;
+    if (a.pro_act == STZS_ACT_LEAKY)
+        return R ? (void (*)(stzs_conv_args))mrfx_conv<STZS_ACT_LEAKY, true, false, 3, 128, 0, true, false, true>
+                 : (void (*)(stzs_conv_args))mrfx_conv<STZS_ACT_LEAKY, false, false, 3, 128, 0, true, false, true>;
+    if (a.pro_act == STZS_ACT_NONE)
+        return R ? (void (*)(stzs_conv_args))mrfx_conv<STZS_ACT_NONE, true, false, 3, 128, 0, true, false, true>
+                 : (void (*)(stzs_conv_args))mrfx_conv<STZS_ACT_NONE, false, false, 3, 128, 0, true, false, true>;
+    return nullptr;
+}
+
 }  // namespace
 
 // the precise FLAT linear (ks 1): validated and launched by stzs_mrfx_conv_launch
@@ -635,7 +694,7 @@ static int mrfx_lin_launch(const stzs_conv_args& a, hipStream_t s) {
 // internal entry used by stzs_conv1d for STZS_CONV_W_FRAG32X3 weights (csrc/dispatch.hip)
 __attribute__((visibility("hidden"))) int stzs_mrfx_conv_launch(const stzs_conv_args& a, hipStream_t s) {
     if (a.in_dtype == STZS_F8 || a.x_scale) return STZS_EDTYPE;
-    if (a.ks == 1) return mrfx_lin_launch(a, s);
+    if (a.ks == 1) return a.t_lens ? STZS_EINVAL : mrfx_lin_launch(a, s);  // (row-local: no lengths)
     // conv_post (128 -> 22, k7, LeakyReLU(0.01), fp32 out): the narrow form, waves split the rows
     const bool narrow = a.Co <= 32 && a.ci_pad == 128 && a.ks == 7 && !a.res && !a.acc_in && !a.stat_part &&
                         a.pro_mode == STZS_PRO_NONE && a.pro_act == STZS_ACT_LEAKY && a.alpha == 1.f &&
@@ -659,8 +718,17 @@ __attribute__((visibility("hidden"))) int stzs_mrfx_conv_launch(const stzs_conv_
     else if (rows64 <= 16 * sb_rows(ks, 64))
         bt = 64;
     if (!bt) return STZS_ESHAPE;
-    void (*k)(stzs_conv_args) = bt == 128 ? pick_form<128>(a) : pick_form<64>(a);
-    if (narrow) k = mrfx_conv<STZS_ACT_LEAKY, false, false, 7, 128, 1, false, true>;
+    void (*k)(stzs_conv_args) = nullptr;
+    if (a.t_lens) {
+        // (stzs_conv_check: the rule common to every form) mode 0: the k3 block forms, mode 1: the Snake forms and the
+        // narrow conv_post form; anything else with lengths is refused here, before any HIP call
+        if (narrow) k = a.t_lens_rows == 1 ? mrfx_conv<STZS_ACT_LEAKY, false, false, 7, 128, 1, false, true, true> : nullptr;
+        else k = pick_rag_form(a, bt);
+        if (!k) return STZS_EINVAL;
+    } else {
+        k = bt == 128 ? pick_form<128>(a) : pick_form<64>(a);
+        if (narrow) k = mrfx_conv<STZS_ACT_LEAKY, false, false, 7, 128, 1, false, true>;
+    }
     if (!k) return STZS_ESHAPE;
     const int rows_in = bt + (ks - 1) * a.dil;
     const size_t lds = (size_t)2 * rows_in * PX + NCS * 128 * 4;

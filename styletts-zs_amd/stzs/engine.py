@@ -1534,10 +1534,23 @@ class StyleTTSZS:
                                    controls=controls)
 
     def _check_ragged_frames(self):
-        """ragged frames run on the default engine's conv forms only: the latency engine's split-K / pair convs and
-        the precise engines' conv_x3 / mrfx forms do not take the lengths (before any launch)"""
-        if self.blk_splitk or self.precise or self.precise_all:
-            raise NotImplementedError("ragged_frames: the default engine only (not blk_splitk / precise engines)")
+        """ragged frames run where the block convs take the lengths: the default engine's forms and the precise
+        engines' mrfx / conv_x3 forms (every fp32 block conv must carry split-operand weights, which a
+        precise engine's packed model does) -- not the latency engine's split-K / pair convs (before any launch)"""
+        if self.blk_splitk:
+            raise NotImplementedError("ragged_frames: not on a blk_splitk (latency) engine -- its split-K / pair "
+                                      "block convs do not take per-row lengths")
+        if self.precise or self.precise_all:
+            # fp32 blocks (the decoder's; with precise_all the predictor's too): their k3 convs take the lengths on the
+            # split-operand forms only -- every one must carry such weights (none packed: nothing to vouch for)
+            W = getattr(self, "W", None)
+            blks = [] if W is None else \
+                [b for b in list(W.dec_blk.values()) + (list(W.pr_blk.values()) if self.precise_all else [])
+                 if hasattr(b, "conv1")]
+            if not blks or not all(getattr(c, "wx3", None) is not None or getattr(c, "fx3", None) is not None
+                                   for b in blks for c in (b.conv1, b.conv2)):
+                raise NotImplementedError("ragged_frames: a precise engine's block convs take per-row lengths on the "
+                                          "split-operand forms (mrfx, conv_x3) only, not on conv_f32")
 
     def prosody_rows(self, pro: dict, rows, T_b: int) -> dict:
         """rows (indices) of a ragged-frames result that share the frame count T_b -> a pro dict decode() accepts for
@@ -1656,7 +1669,7 @@ class StyleTTSZS:
         alignment's total[b], read on the device by every later kernel (no host sync), returned as "frame_lens".
         Row b's idx / en / aligned text rows / F0[b, :2 T_b] / N[b, :2 T_b] are those of the row alone at T40 = T_b;
         past it idx is -1, en and the aligned text rows are zeros, F0 / N finite and unspecified (prosody_rows cuts
-        the rows of one frame count out for decode()).  The default engine only (NotImplementedError otherwise).
+        the rows of one frame count out for decode()).  Not on a blk_splitk engine (NotImplementedError).
         controls: their pitch_shift, as f0n_predictor (dur already holds the rows' rates)."""
         if ragged_frames:
             self._check_ragged_frames()
@@ -1973,21 +1986,29 @@ class StyleTTSZS:
 
     def _check_ragged_decoder(self):
         """the ragged decoder runs where every generator conv takes a form with length-aware kernels
-        (stzs_conv_args.t_lens_rows = 1): the default bf16 engine -- not the latency engine's split-K blocks, not a
-        precise or fp32-decoder engine -- on a spec whose MRF convs and ConvTransposes are on the register-direct form
-        and whose conv_post is on the narrow form (SPEC_V0; not SPEC_TINY's generic convs).  Before any launch."""
+        (stzs_conv_args.t_lens_rows = 1).  Not the latency engine's split-K blocks.  A precise decoder (precise=True
+        or precise_decoder=True, fp32 rows): every generator conv has split-operand weights, so it routes to the mrfx or
+        the conv_x3 form, which both take the lengths -- an fp32 decoder whose convs would run on
+        conv_f32 is refused.  The bf16 decoder: a spec whose MRF convs and ConvTransposes are on the register-direct
+        form and whose conv_post is on the narrow form (SPEC_V0; not SPEC_TINY's generic convs).  Before any launch."""
         self._check_ragged_frames()
+        W = getattr(self, "W", None)  # (no packed weights: no form can be vouched for)
         if self.dec_dt != torch.bfloat16:
-            raise NotImplementedError("ragged decoder: the bf16 decoder only")
-        W = self.W
-        ok = all(getattr(lw[c], "frag32", False) and lw["k"] in (3, 7, 11)
-                 for st in W.rb for res in st for lw in res for c in ("c1", "c2"))
+            gen = [] if W is None else \
+                [lw[c] for st in W.rb for res in st for lw in res for c in ("c1", "c2")] + list(W.ups) + [W.conv_post]
+            if not gen or not all(getattr(cw, "wx3", None) is not None or getattr(cw, "fx3", None) is not None
+                                  for cw in gen):
+                raise NotImplementedError("ragged decoder: an fp32 decoder takes per-row lengths on the split-operand "
+                                          "forms (mrfx, conv_x3) only, not on conv_f32 (STZS_CONV_W_F32)")
+            return
+        ok = W is not None and all(getattr(lw[c], "frag32", False) and lw["k"] in (3, 7, 11)
+                                   for st in W.rb for res in st for lw in res for c in ("c1", "c2"))
         ok = ok and all(getattr(u, "frag32", False) and u.ci_pad // 128 <= 4 for u in W.ups)
         ok = ok and getattr(W.conv_post, "narrow32", False)
         if not ok:
-            raise NotImplementedError("ragged decoder: the generator's MRF convs and ConvTransposes must take the "
-                                      "register-direct form and conv_post the narrow form (generic-path convs do "
-                                      "not take per-row lengths)")
+            raise NotImplementedError("ragged decoder: a bf16 generator's MRF convs and ConvTransposes must take the "
+                                      "register-direct form and conv_post the narrow form (generic-path bf16 convs "
+                                      "do not take per-row lengths; neither do conv_f32 or the blk_splitk blocks)")
 
     def dec_style(self, codes: torch.Tensor) -> torch.Tensor:
         """every AdaIN gamma / beta of the decoder from the pooled acoustic codes: ONE GEMM -> [B, total] fp32."""

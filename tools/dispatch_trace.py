@@ -11,6 +11,7 @@ route every traced call to the same kernels with the same launch geometry: the c
     python tools/dispatch_trace.py --coverage a.txt b.txt            # registered conv-family kernels never launched
     python tools/dispatch_trace.py --linear-cases --out d.txt        # the identity-probe table of the linears' GPU test
     python tools/dispatch_trace.py --precise-cases --out e.txt       # every launch of the precise convs' GPU test
+    python tools/dispatch_trace.py --ragged-precise-cases --out f.txt   # the precise convs with per-row lengths (§2i)
 
 Trace lines (hip_record.cpp): "L kernel gx gy gz bx by bz lds", "A kernel attribute value" (hipFuncSetAttribute),
 "C memcpy|memset bytes", "M text" (this driver's markers: "case NAME" before a synthesis case, "call LABEL" / "rc N"
@@ -401,9 +402,10 @@ def sweep_calls():
                    ("frag32 ups", conv(Ci=256, Co=128, ups=4, cic=128, flags=FRAG32, pro_act=LEAKY, t_lens=TL)),
                    ("lane16", conv(Ci=256, ks=3, cic=128, flags=LANE16, pro_act=LEAKY, t_lens=TL)),
                    ("narrow32", conv(Ci=128, Co=22, ks=7, cic=128, flags=NARROW32, outd=F32, pro_act=LEAKY, ldy=24, t_lens=TL)),
-                   ("x3", conv(Ci=64, ks=3, flags=X3, ind=F32, outd=F32, t_lens=TL)),
+                   # (the precise forms take fp32 rows with lengths, --ragged-precise-cases: what they still refuse)
+                   ("x3 bf16", conv(Ci=64, ks=3, flags=X3, ind=BF16, outd=BF16, t_lens=TL)),
                    ("f32", conv(Ci=64, ks=3, flags=WF32, ind=F32, outd=F32, t_lens=TL)),
-                   ("x3frag", conv(Ci=256, ks=3, cic=128, flags=FRAG32X3, ind=F32, outd=F32, pro_act=LEAKY, t_lens=TL)),
+                   ("x3frag ks 7", conv(Ci=256, ks=7, cic=128, flags=FRAG32X3, ind=F32, outd=F32, pro_act=LEAKY, t_lens=TL)),
                    ("rows", conv(B=1, T=20, Ci=512, Co=200, flags=ROWS, t_lens=TL))):
         one(f"tlens.bad {lab}", d)
 
@@ -453,8 +455,9 @@ def sweep_calls():
     for lab, d in (("mfma snake", conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, adain=True, pro_act=SNAKE, **TR)),
                    ("mfma leaky", conv(B=4, T=200, Ci=64, Co=32, ks=3, cic=64, adain=True, pro_act=LEAKY, **TR)),
                    ("lane16", conv(Ci=256, ks=3, cic=128, flags=LANE16, pro_act=SNAKE, **TR)),
-                   ("x3frag", conv(Ci=256, ks=3, cic=128, flags=FRAG32X3, ind=F32, outd=F32, pro_act=SNAKE, **TR)),
-                   ("x3", conv(Ci=64, ks=3, flags=X3, ind=F32, outd=F32, **TR)),
+                   # (the precise forms take fp32 rows with row counts, --ragged-precise-cases: never bf16 rows)
+                   ("x3frag bf16", conv(Ci=256, ks=3, cic=128, flags=FRAG32X3, ind=BF16, outd=BF16, pro_act=SNAKE, **TR)),
+                   ("x3 bf16", conv(Ci=64, ks=3, flags=X3, ind=BF16, outd=BF16, **TR)),
                    ("rows", conv(B=1, T=20, Ci=512, Co=200, flags=ROWS, **TR)),
                    ("glds", conv(Ci=256, flags=A_DMA, **TR)),
                    ("splitk", dict(s3, B=1, splitk=2, splitk_ws=PTR["splitk_ws"], splitk_ctr=PTR["splitk_ctr"])),
@@ -595,6 +598,53 @@ def precise_cases(lib, out):
     print(f"precise cases: {n} -> {out}")
 
 
+# ---- mode (e): the precise convs with per-row lengths ---------------------------------------------------------------
+def ragged_precise_args(c, lengths=True):
+    """a case of tests/ragged_precise_cases.py -> the stzs_conv_args fields (fixed fake pointers); lengths=False: the
+    same problem without t_lens (its non-ragged sibling)"""
+    fx3 = c["form"] == "fx3"
+    act = {"snake": SNAKE, "leaky": LEAKY, "none": NONE}[c["act"]]
+    d = conv(B=c["B"], T=c["T"], Ci=c["Ci"], Co=c["Co"], ks=c["ks"], dil=c["dil"], cic=128 if fx3 else 32,
+             flags=FRAG32X3 if fx3 else X3, ind=F32, outd=F32, res=c["res"], acc=c["acc"], pro_act=act, adain=c["adain"],
+             stat=c["stat"], alpha=c["alpha"], ups=c["ups"], res_tdiv=c["tdiv"], refl=c["refl"])
+    d["ci_pad"] = rup(c["Ci"], 128 if c["Ci"] > 64 else 64 if c["Ci"] > 32 else 32)  # (stzs/weights.py pack_conv)
+    d["ldx"], d["bsx"] = d["ci_pad"], c["T"] * d["ci_pad"]
+    if c["Co"] == 22:  # (conv_post: 24-column rows)
+        d["ldy"], d["bsy"] = 24, c["T"] * 24
+    if c["ups"]:
+        d["ups_pad"] = c["ups"] // 2
+    if lengths:
+        d.update(t_lens=PTR["t_lens"], t_lens_rows=c["mode"], t_lens_mul=c["mul"])
+    d.update(c["over"])
+    return d
+
+
+def ragged_precise_cases(lib, out):
+    """every launch shape of tests/test_gpu_ragged_precise_kernels.py (tests/ragged_precise_cases.py) through the native
+    dispatch: "call rag <label>" with the lengths, "call uni <label>" the same problem without them (the non-ragged
+    sibling: same grid, same LDS bytes, the kernel without RAG), "call bad <label>" the refusals"""
+    L = _load(lib, out)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ragged_precise_cases as RP
+    from stzs import _lib
+
+    def call(label, d):
+        a = _lib.ConvArgs()
+        for f, v in d.items():
+            setattr(a, f, v)
+        L.hip_record_mark(f"call {label}".encode())
+        rc = L.stzs_conv1d(C.byref(a), None)
+        L.hip_record_mark(f"rc {rc}".encode())
+
+    acc, bad = RP.accepted(), RP.refused()
+    for c in acc:
+        call("rag " + c["label"], ragged_precise_args(c))
+        call("uni " + c["label"], ragged_precise_args(c, lengths=False))
+    for c in bad:
+        call("bad " + c["label"], ragged_precise_args(c))
+    print(f"ragged precise cases: {len(acc)} accepted (each with its non-ragged sibling), {len(bad)} refused -> {out}")
+
+
 # ---- coverage -----------------------------------------------------------------------------------------------------
 def registered(objdir, names=CONV_OBJECTS):
     """{object: set of registered kernel names}, from the objects' host stubs (nm)"""
@@ -637,6 +687,7 @@ def main():
     g.add_argument("--coverage", nargs="+", metavar="TRACE")
     g.add_argument("--linear-cases", action="store_true")
     g.add_argument("--precise-cases", action="store_true")
+    g.add_argument("--ragged-precise-cases", action="store_true")
     a = ap.parse_args()
     if a.coverage:
         return coverage(a.objects, a.coverage)
@@ -648,6 +699,8 @@ def main():
         linear_cases(lib, out)
     elif a.precise_cases:
         precise_cases(lib, out)
+    elif a.ragged_precise_cases:
+        ragged_precise_cases(lib, out)
     else:
         sweep(lib, out)
 

@@ -11,8 +11,11 @@ around synth() ending in a device synchronise -- and the medians, the phase-1 ba
 (each phase-1 batch ends in a host sync, so the scheduler's own clock is the phase's) and the share of the phase-1
 reference blocks that is padding go out as one JSON line.
 
-    python tools/ragged_traffic.py [--requests 64] [--runs 7] [--warmup 2] [--ref-s LO,HI]
+    python tools/ragged_traffic.py [--requests 64] [--runs 7] [--warmup 2] [--ref-s LO,HI] [--engine default|precise]
                                    [--mode both|all|plain|ragged|ragged_ref|ragged_frames|ragged_decoder|controls]
+
+--engine precise: the same protocol on StyleTTSZS(precise=True), whose convs take the lengths on the
+mrfx / conv_x3 forms.
 
 --mode both: plain and ragged (the measurement of "Ragged text batches"); all: the five schedules.
 
@@ -119,6 +122,8 @@ def main():
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--mode", choices=("both", "all", "plain", "ragged", "ragged_ref", "ragged_frames", "ragged_decoder",
                                        "controls"), default="both")
+    ap.add_argument("--engine", choices=("default", "precise"), default="default",
+                    help="the engine under the schedulers: the bf16 default, or StyleTTSZS(precise=True)")
     ap.add_argument("--ref-s", default=None, metavar="LO,HI",
                     help="reference lengths seeded uniformly in [LO, HI] seconds (default: 3 s for every request)")
     a = ap.parse_args()
@@ -133,7 +138,7 @@ def main():
     from stzs.spec import SPEC_V0 as S
     if not torch.cuda.is_available():
         raise SystemExit("ragged_traffic.py measures on the GPU: none is visible")
-    eng = StyleTTSZS(S, init_params(S, seed=0), device="cuda:0")
+    eng = StyleTTSZS(S, init_params(S, seed=0), device="cuda:0", precise=a.engine == "precise")
     reqs = make_requests(S, a.requests, ref_s=ref_s)
     if a.mode == "controls":
         print(json.dumps(controls_mode(a, eng, S, reqs)))
@@ -168,7 +173,7 @@ def main():
             dt, _ = run(m)
             wall[m].append(1e3 * dt)
             ph1[m].append(sch[m].stats["phase1_ms"])
-    res = dict(requests=a.requests, tokens=[int(r.tokens.shape[0]) for r in reqs], steps=STEPS, cfg=CFG,
+    res = dict(engine=a.engine, requests=a.requests, tokens=[int(r.tokens.shape[0]) for r in reqs], steps=STEPS, cfg=CFG,
                ref_s=REF_S if ref_s is None else list(ref_s), runs=a.runs, warmup=a.warmup)
     if ref_s is not None:
         res["ref_samples"] = [int(r.ref_wav.shape[0]) for r in reqs]
