@@ -735,6 +735,39 @@ typedef struct stzs_vq_args {
 } stzs_vq_args;
 int stzs_code_quantize(const stzs_vq_args* a, void* stream);
 
+/* ---- enrolled voices: a device-resident voice bank + per-row sources -> prompt rows, one launch ----
+ * A voice is the pre-quantiser prompt features of its reference (zbank [V, L, C] fp32, C = G * dg; bank row (v, l) at
+ * zbank[(v * L + l) * ldz]) and their product-VQ indices (ibank [V, L, G] int32, row stride ldib).  Row r = b * L + l of
+ * the batch reads n = clamp(cnt[b], 1, Kmax) sources s_k = clamp(src[b * Kmax + k], 0, V - 1) with weights
+ * w[b * Kmax + k], all device arrays (entries k >= n are never read):
+ *   gather == 0 (mix form)   acc = w_0 * z[s_0][l];  acc = acc + (w_k * z[s_k][l]) for k = 1 .. n - 1, elementwise,
+ *       every product and every sum rounded to fp32 on its own (no contraction: numpy float32 arithmetic in this order
+ *       gives the bits); then the product VQ of acc exactly as stzs_code_quantize computes it (the same explicitly
+ *       rounded distance, the first minimum winning): idx[r * ldi + g], y[r * ldy + ...] as there, and, where zmix is
+ *       not NULL, zmix[r * ldm + ...] = acc.  One workgroup per (64 rows, group), the group's codebook in LDS.
+ *   gather != 0 (gather form)  for rows the caller knows to be ONE voice at weight 1: idx = ibank[s_0][l] (clamped
+ *       into [0, K) before it addresses the codebook), y = those codebook rows, zmix = z[s_0][l]; w and cnt are not
+ *       read.  No LDS, no scan.  With a bank whose ibank is the mix form's idx of its zbank this is the mix form at
+ *       cnt = 1, w = 1, bit for bit (1.0f * z is z).
+ * Checked before any HIP call -- STZS_EINVAL: a NULL zbank / codebook / src / w / cnt / idx / y, gather without ibank,
+ * a pointer not 4-byte aligned; STZS_ESHAPE: V, L, B, G, K or Kmax <= 0, Kmax > 8, dg outside {4, 8, 16}, a codebook
+ * of one group over 64 KB of LDS (K * dg * 4 + 2048 bytes), ldz / ldy (/ ldm with zmix) < G * dg, ldi (/ ldib with
+ * gather) < G, G > 65535, B * L or V * L past 2^31 - 1. */
+typedef struct stzs_voice_args {
+    const float* zbank;     /* [V, L, C] f32 */
+    const int32_t* ibank;   /* [V, L, G] int32: the gather form's input (may be NULL in the mix form) */
+    const float* codebook;  /* [G][K][dg] f32 */
+    const int32_t* src;     /* int32 [B, Kmax] voice ids */
+    const float* w;         /* f32 [B, Kmax] weights */
+    const int32_t* cnt;     /* int32 [B] sources per row */
+    int32_t* idx;           /* int32 [B, L, G] out */
+    float* y;               /* f32 [B, L, C] out: dequantised rows */
+    float* zmix;            /* optional f32 [B, L, C] out: the mixed pre-quantiser rows (NULL: not written) */
+    int64_t ldz, ldib, ldi, ldy, ldm;
+    int32_t V, L, B, Kmax, G, K, dg, gather;
+} stzs_voice_args;
+int stzs_voice_prompt(const stzs_voice_args* a, void* stream);
+
 /* ---- sampler glue ---- */
 /* c[r, j] = silu(pool[r, j] + temb[j]) -> bf16 */
 int stzs_dn_cond(const float* pool, const float* temb, void* c, int R, int D, void* stream);

@@ -36,7 +36,11 @@ FILE_FLAGS = {"source.hip": NO_PK, "conv.hip": NO_PK, "gemm.hip": NO_PK, "convx.
               # (r06, for speed, not the hazard: the stage-1 MRF convs' staging VALU beside MFMAs, csrc/mrfv_n1.hip)
               "mrfv_n1.hip": NO_PK,
               # the resampler's independent fp32 FMA chains (csrc/resample.hip): the hazard form again
-              "resample.hip": NO_PK}
+              "resample.hip": NO_PK,
+              # the voice mix's independent per-lane fp32 mul / add chains (csrc/voice.hip): the hazard form again; and
+              # no contraction at all in that file -- its definition is separately rounded products and sums, and under
+              # -ffp-contract=fast the backend fuses a multiply into an add whatever the source says
+              "voice.hip": NO_PK + ["-ffp-contract=off"]}
 
 
 def sources():

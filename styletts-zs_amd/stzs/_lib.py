@@ -208,6 +208,14 @@ class VqArgs(C.Structure):
                [(n, i32) for n in ("R", "G", "K", "dg", "lookup", "pad_i")]
 
 
+class VoiceArgs(C.Structure):
+    """stzs_voice_prompt: a voice bank + per-row sources -> prompt rows (mix form | gather form)"""
+    _fields_ = [(n, vp) for n in ("zbank",)] + [("ibank", opt_vp)] + \
+               [(n, vp) for n in ("codebook", "src", "w", "cnt", "idx", "y")] + [("zmix", opt_vp)] + \
+               [(n, i64) for n in ("ldz", "ldib", "ldi", "ldy", "ldm")] + \
+               [(n, i32) for n in ("V", "L", "B", "Kmax", "G", "K", "dg", "gather")]
+
+
 class CopyArgs(C.Structure):
     _fields_ = [("x", vp), ("y", vp)] + [(n, i64) for n in ("ldx", "bsx", "ldy", "bsy")] + \
                [(n, i32) for n in ("B", "R", "C", "in_dtype", "out_dtype", "pad_i")] + [("dst_row_off", vp)]
@@ -264,6 +272,7 @@ EXPORTS = ["stzs_init", "stzs_strerror", "stzs_version", "stzs_conv1d", "stzs_co
            "stzs_durations", "stzs_alignment", "stzs_gather_rows", "stzs_adain_dwup", "stzs_f0n_down",
            "stzs_harmonic_source", "stzs_istft", "stzs_istft_stream", "stzs_istft_stream_span",
            "stzs_stft_frames", "stzs_log_mel", "stzs_stft_logmel", "stzs_pool_rows", "stzs_mask_rows", "stzs_code_quantize",
+           "stzs_voice_prompt",
            "stzs_dn_cond", "stzs_dn_cond_steps", "stzs_adaln_expand", "stzs_cfg_euler", "stzs_cfg_euler_rows", "stzs_row_scale",
            "stzs_resample", "stzs_state_init", "stzs_mean_rows", "stzs_copy2d", "stzs_frame_rows", "stzs_embed", "stzs_embed_f32", "stzs_embed_lens", "stzs_dn_cond_steps_f32", "stzs_pack_conv_size", "stzs_pack_conv",
            "stzs_pack_lstm", "stzs_pack_lstm_x3"] + [f"stzs_{o}{sfx}" for o in GENERIC_OPS for sfx in ("", "_workspace")]
@@ -322,6 +331,7 @@ def load():
         "stzs_pool_rows": ([P(PoolArgs), vp], i32),
         "stzs_mask_rows": ([P(MaskArgs), vp], i32),
         "stzs_code_quantize": ([P(VqArgs), vp], i32),
+        "stzs_voice_prompt": ([P(VoiceArgs), vp], i32),
         "stzs_dn_cond_steps": ([vp, vp, vp, i32, i32, i32, vp], i32),
         "stzs_dn_cond_steps_f32": ([vp, vp, vp, i32, i32, i32, vp], i32),
         "stzs_dn_cond":([vp, vp, vp, i32, i32, vp], i32),

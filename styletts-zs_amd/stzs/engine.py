@@ -28,6 +28,7 @@ import torch
 
 from . import _lib as L
 from . import resample as RS
+from . import voice as VC
 from .spec import Spec
 from .weights import ConvW, PackedModel
 
@@ -1243,6 +1244,96 @@ class StyleTTSZS:
         out = self.buf("prompt.z", (B, S.L_s, S.code_dim), torch.float32)
         self.conv(W.pe_proj, pooled, Act(out), what="pe.proj")
         return out
+
+    # ------------------------------------------------------------------ enrolled voices
+    def voice_prompt(self, zbank: torch.Tensor, ibank, src: torch.Tensor, w: torch.Tensor, cnt: torch.Tensor,
+                     idx: torch.Tensor, out: torch.Tensor, zmix: torch.Tensor = None, gather=False):
+        """one stzs_voice_prompt launch: zbank fp32 [V, L, code] (ibank int32 [V, L, G]: the gather form's input), src
+        int32 [B, Kmax], w fp32 [B, Kmax], cnt int32 [B] on the device -> idx int32 [B, L, G], out fp32 [B, L, code]
+        (the dequantised rows), zmix fp32 [B, L, code] (optional: the mixed pre-quantiser rows)"""
+        S, W = self.spec, self.W
+        G = S.code_dim // S.vq_group
+        a = L.VoiceArgs()
+        a.zbank, a.ibank = zbank.data_ptr(), (ibank.data_ptr() if ibank is not None else None)
+        a.codebook, a.src, a.w, a.cnt = W.t(W.pe_vq).data_ptr(), src.data_ptr(), w.data_ptr(), cnt.data_ptr()
+        a.idx, a.y, a.zmix = idx.data_ptr(), out.data_ptr(), (zmix.data_ptr() if zmix is not None else None)
+        a.ldz, a.ldib, a.ldi, a.ldy, a.ldm = S.code_dim, G, G, S.code_dim, S.code_dim
+        a.V, a.L, a.B, a.Kmax = zbank.shape[0], zbank.shape[1], idx.shape[0], src.shape[1]
+        a.G, a.K, a.dg, a.gather = G, S.vq_size, S.vq_group, int(bool(gather))
+        self._call(self.lib.stzs_voice_prompt, a, "voice_prompt")
+
+    def voice_encode(self, voices: "VC.VoiceRows") -> torch.Tensor:
+        """the prompt of a batch from enrolled voices, ONE launch: -> the dequantised codes fp32 [B, L_s, code], what
+        prompt_encode returns; the indices stay in self.prompt_idx.  The kernel reads the rows' device arrays (and the
+        bank's) when it runs: a captured graph replays with what VoiceRows.set() / VoiceBank.replace() wrote."""
+        S = self.spec
+        B = voices.B
+        G = S.code_dim // S.vq_group
+        bank = voices.bank
+        if tuple(bank.z.shape[1:]) != (S.L_s, S.code_dim) or bank.z.device != self.device or \
+                voices.src.device != self.device or (bank.idx is None and voices.gather) or \
+                (bank.idx is not None and tuple(bank.idx.shape) != (bank.z.shape[0], S.L_s, G)):
+            raise ValueError("voices: the bank or the rows do not belong to this engine (shape / device)")
+        idx = self.buf("prompt.idx", (B, S.L_s, G), torch.int32)
+        out = self.buf("prompt", (B, S.L_s, S.code_dim), torch.float32)
+        self.voice_prompt(bank.z, bank.idx, voices.src, voices.w, voices.cnt, idx, out, gather=voices.gather)
+        self.prompt_idx = idx
+        return out
+
+    def voice_fingerprint(self) -> str:
+        """what a Voice must carry to be used with this engine (stzs/voice.py engine_fingerprint)"""
+        return VC.engine_fingerprint(self)
+
+    def enroll(self, ref_wav, ref_lens=None, ref_sr=None, weights=None) -> "VC.Voice":
+        """enrol a voice: ref_wav fp32 [N], or [K, N] -- K <= 8 clips of one speaker, zero-padded and
+        ragged through ref_lens, at any rate through ref_sr (both as synth() takes them) -> Voice.  The K clips run as
+        ONE prompt_features batch; one stzs_voice_prompt launch in the mix form then forms
+        z = sum_k w_k z_k, w_k = float32(weights_k / sum(weights)) (float64 on the host; default: equal), and its
+        discrete codes.  With one clip the weight is exactly 1.0 and the voice holds, bit for bit, what
+        prompt_features / prompt_encode give for the clip.  ValueError -- before any launch -- for K > 8, a
+        non-finite or negative weight, a zero sum."""
+        S = self.spec
+        wav = torch.as_tensor(ref_wav)
+        if wav.dim() == 1:
+            wav = wav[None]
+        if wav.dim() != 2 or not wav.dtype.is_floating_point:
+            raise ValueError(f"enroll: ref_wav must be a float [N] or [K, N] tensor, got {tuple(wav.shape)} {wav.dtype}")
+        K = wav.shape[0]
+        if not 1 <= K <= VC.KMAX:
+            raise ValueError(f"enroll: {K} clips (1 to {VC.KMAX} per voice)")
+        w = VC.normalise_weights(weights, K, "enroll: weights")
+        if ref_sr is not None:
+            wav, ref_lens = self._ref_in(wav, ref_sr, ref_lens, None)
+        z = self.prompt_features(wav, ref_lens)
+        G = S.code_dim // S.vq_group
+        dev = self.device
+        src = torch.arange(K, dtype=torch.int32).reshape(1, K).to(dev)
+        wd = torch.tensor([w], dtype=torch.float32).to(dev)
+        cnt = torch.tensor([K], dtype=torch.int32).to(dev)
+        idx = torch.empty(1, S.L_s, G, dtype=torch.int32, device=dev)
+        q = torch.empty(1, S.L_s, S.code_dim, dtype=torch.float32, device=dev)
+        zmix = torch.empty(1, S.L_s, S.code_dim, dtype=torch.float32, device=dev)
+        self.voice_prompt(z, None, src, wd, cnt, idx, q, zmix)
+        return VC.Voice(zmix[0], idx[0], self.voice_fingerprint(), K, "precise" if self.precise_frontend else "bf16")
+
+    def voice_rows(self, B: int, bank, ids, weights=None) -> "VC.VoiceRows":
+        """the speakers of a batch of B rows (VoiceRows): ids is B voice ids of `bank` (one voice per
+        row: the gather form), or B id sequences with B weight sequences (blends, rows of different source counts: the
+        mix form; weights None: equal).  Host values are range-checked (ValueError) and uploaded once into device
+        arrays the result owns; hand it to synth / synth_stream / encode_inputs as voices=."""
+        return VC.VoiceRows(B, bank, ids, weights, self.device)
+
+    def _check_voices(self, voices, tokens, ref_wav=None, prompt_idx=None, ref_lens=None, ref_sr=None):
+        """voices= excludes every other source of the prompt, and is made for the batch's row count: ValueError,
+        before any launch"""
+        if voices is None:
+            return
+        for name, v in (("ref_wav", ref_wav), ("prompt_idx", prompt_idx), ("ref_lens", ref_lens), ("ref_sr", ref_sr)):
+            if v is not None:
+                raise ValueError(f"voices= and {name}= were both given: the prompt comes from one or the other")
+        if not isinstance(voices, VC.VoiceRows):
+            raise ValueError(f"voices must be VoiceRows (voice_rows()), got {type(voices).__name__}")
+        voices.rows(tokens.shape[0])
 
     # ------------------------------------------------------------------ (a) style diffusion
     def sample_style(self, h_txt: Act, prompt: torch.Tensor, eps: torch.Tensor, steps: int,
@@ -2623,10 +2714,14 @@ class StyleTTSZS:
         t.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         return t
 
-    def encode_inputs(self, tokens, ref_wav, prompt_idx=None, text_lens=None, ref_lens=None):
+    def encode_inputs(self, tokens, ref_wav, prompt_idx=None, text_lens=None, ref_lens=None, voices=None):
         """text encoder || prompt encoder (independent; forked when branch_streams) -> (h_txt, prompt codes).
         ref_lens: per-row sample counts of a ragged reference batch; host lengths are checked and uploaded here, on
-        the current stream, before the fork (the forked prompt branch waits on it)."""
+        the current stream, before the fork (the forked prompt branch waits on it).
+        voices (VoiceRows; ref_wav None): the prompt branch is one stzs_voice_prompt launch (voice_encode)."""
+        if voices is not None:
+            self._check_voices(voices, tokens, ref_wav, prompt_idx, ref_lens)
+            return self.fork("enc", lambda: self.text_encode(tokens, text_lens), lambda: self.voice_encode(voices))
         ref = None if ref_wav is None else ref_wav.to(self.device)
         if prompt_idx is not None or ref is None:
             ref_lens = None  # (teacher-forced codes: the reference and its lengths are unused)
@@ -2660,7 +2755,7 @@ class StyleTTSZS:
 
     def synth(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None, codes=None,
               n_frames=None, prompt_idx=None, check=True, text_lens=None, ref_lens=None, ragged_frames=False,
-              controls: RowControls = None, ref_sr=None, out_sr=None, out_dtype=None):
+              controls: RowControls = None, ref_sr=None, out_sr=None, out_dtype=None, voices=None):
         """tokens int [B, T_txt]; ref_wav fp32 [B|1, N]; noise fp32 [B, L_s, code]; durations int [B, T_txt]
         (host tensor, or device tensor + n_frames: no device sync); seeds: per-utterance source-noise
         seeds; prompt_idx: teacher-forced discrete prompt codes [B|1, L_s, G] (ref_wav then unused).
@@ -2685,16 +2780,21 @@ class StyleTTSZS:
         (16-bit PCM) or fp32, one launch behind the decoder: "wav" is at out_sr and the dict gains "sr"; with
         ragged_frames row b is valid to ceil(600 frame_lens[b] out_sr / sr) and exact zeros from there.  All None: no
         launch is added.
+        voices (voice_rows()): the speakers as enrolled voices, one or a blend per row -- ref_wav is
+        then None and the prompt front end is ONE launch (stzs_voice_prompt); with any of ref_wav, prompt_idx, ref_lens
+        or ref_sr: ValueError before any launch.  Device arrays: a captured synth() replays for the speakers
+        VoiceRows.set() wrote.
         check: raise RuntimeError if an LSTM exchange of this call timed out (its durations / prosody would be
         wrong) -- one 4-B device read, skipped while a graph is being captured (CheckedGraph.check() then);
         check=False leaves it to the caller (check_status(), or the returned `status` word).
         -> dict(wav=[B, 600*T40], prompt_idx=[B|1, L_s, G], status=int32 [1], ...)"""
+        self._check_voices(voices, tokens, ref_wav, prompt_idx, ref_lens, ref_sr)
         if ragged_frames:
             self._check_ragged_decoder()
         self._check_out(out_sr, out_dtype)
         h, prompt, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
                                                    n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls,
-                                                   ref_sr)
+                                                   ref_sr, voices)
         wav = self.decode(pro, codes, seeds, frame_lens=pro["frame_lens"] if ragged_frames else None)
         wav = self._wav_out(wav, out_sr, out_dtype, pro["frame_lens"] if ragged_frames else None)
         if check and not self._capturing():
@@ -2707,18 +2807,23 @@ class StyleTTSZS:
         return out
 
     def _front(self, tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes, n_frames, prompt_idx,
-               text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None, ref_sr=None):
+               text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None, ref_sr=None,
+               voices=None):
         """everything before the decoder, shared by synth() and synth_stream(): tokens to the device, text || prompt
         encoders (one prompt broadcast over the batch), style sampling unless codes are given, prosody, default seeds
         -> (h_txt, prompt, codes, pro, seeds); the prompt's discrete codes are in self.prompt_idx"""
         S = self.spec
         dev = self.device
+        self._check_voices(voices, tokens, ref_wav, prompt_idx, ref_lens, ref_sr)
         tokens = tokens.to(dev, torch.int32) if tokens.device != dev or tokens.dtype != torch.int32 else tokens
         B = tokens.shape[0]
         text_lens = self.text_lens(text_lens, B, tokens.shape[1])  # (host lengths: checked and uploaded once)
         if ref_sr is not None:  # (a reference at another rate: converted on this stream, before the encoders fork)
             ref_wav, ref_lens = self._ref_in(ref_wav, ref_sr, ref_lens, prompt_idx)
-        h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx, text_lens, ref_lens)
+        if voices is not None:
+            h, prompt = self.encode_inputs(tokens, None, None, text_lens, None, voices)
+        else:
+            h, prompt = self.encode_inputs(tokens, ref_wav, prompt_idx, text_lens, ref_lens)
         if prompt.shape[0] == 1 and B > 1:
             pe = self.buf("prompt.bc", (B, S.L_s, S.code_dim), torch.float32)
             pe.copy_(prompt.expand(B, -1, -1))
@@ -2731,7 +2836,7 @@ class StyleTTSZS:
     def synth_stream(self, tokens, ref_wav, steps=2, cfg_scale=1.0, noise=None, durations=None, seeds=None,
                      codes=None, n_frames=None, chunk_s=1.0, prompt_idx=None, check=True, chunked_halo=None,
                      text_lens=None, ref_lens=None, ragged_frames=False, controls: RowControls = None, ref_sr=None,
-                     out_sr=None, out_dtype=None):
+                     out_sr=None, out_dtype=None, voices=None):
         """configs[4] long-form synthesis with the streaming iSTFT decoder: the text,
         style, prosody and conv stack run over the whole target (AdaIN instance statistics are
         utterance-global), then the waveform is emitted in `chunk_s`-second chunks.  Yields
@@ -2750,12 +2855,15 @@ class StyleTTSZS:
         goes through one chunked conversion (Resampler.stream: one launch per chunk, and one for the filter's tail
         behind the last); the pairs are (first_out_sample, chunk) at out_sr, contiguous, and their concatenation is
         the bits of the one-shot conversion of the unconverted stream -- with ragged_frames of its rows alone, row b
-        valid to ceil(600 frame_lens[b] out_sr / sr)."""
+        valid to ceil(600 frame_lens[b] out_sr / sr).
+        voices: the speakers as enrolled voices (ref_wav None), as synth()."""
+        self._check_voices(voices, tokens, ref_wav, prompt_idx, ref_lens, ref_sr)
         if ragged_frames:
             self._check_ragged_decoder()
         self._check_out(out_sr, out_dtype)
         _, _, codes, pro, seeds = self._front(tokens, ref_wav, steps, cfg_scale, noise, durations, seeds, codes,
-                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls, ref_sr)
+                                              n_frames, prompt_idx, text_lens, ref_lens, ragged_frames, controls, ref_sr,
+                                              voices)
         fl = None
         if ragged_frames:
             fl = self.frame_lens = pro["frame_lens"]

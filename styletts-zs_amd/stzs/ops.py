@@ -21,6 +21,8 @@ operators pin the L1 surface SURVEY §8(b) lists, one per hot-path row of §8(a)
   stzs::mrf_resblock     a12     the MRF of one generator stage (AdaIN + Snake + dilated convs)
   stzs::conv_post_istft  a13     conv_post + exp/sin spectrum + iSTFT
   stzs::code_quantize    (f)1    the discrete style-code quantiser (README.md:5)
+  stzs::voice_prompt     §2j     enrolled voices: a voice bank + per-row sources -> prompt codes, one launch
+  stzs::synth_voices     §2j     stzs::synth with the speakers as enrolled voices in place of the reference wav
   stzs::resample         §2h     sample-rate conversion, fp32 or 16-bit PCM out (no engine handle)
 
 Model-bound operators take an integer engine handle from `register(engine)` (the packed weights live in
@@ -462,6 +464,59 @@ def _(handle, z):
     return z.new_empty((z.shape[0], z.shape[1], G), dtype=torch.int32), z.new_empty(z.shape, dtype=torch.float32)
 
 
+@custom_op("stzs::synth_voices", mutates_args=(), device_types="cuda")
+def synth_voices(handle: int, tokens: torch.Tensor, zbank: torch.Tensor, ibank: Optional[torch.Tensor],
+                 src: torch.Tensor, w: torch.Tensor, cnt: torch.Tensor, noise: torch.Tensor, durations: torch.Tensor,
+                 steps: int, cfg_scale: float, seeds: List[int]) -> torch.Tensor:
+    """stzs::synth with the speakers as enrolled voices (DESIGN.md §2j) in place of ref_wav: the bank and the per-row
+    device arrays of stzs::voice_prompt (ibank given: the gather form; None: the mix form) -> waveform."""
+    from . import voice as VC
+    eng = _eng(handle, tokens, zbank, ibank, src, w, cnt, noise)
+    bank = VC._Stack(z=zbank.float().contiguous(), idx=None if ibank is None else ibank.to(torch.int32).contiguous())
+    rows = VC.VoiceRows.from_device(bank, src.to(torch.int32).contiguous(), w.float().contiguous(),
+                                    cnt.to(torch.int32).contiguous(), ibank is not None)
+    out = eng.synth(tokens, None, steps=steps, cfg_scale=cfg_scale, noise=noise, durations=durations.cpu(),
+                    seeds=list(seeds), voices=rows)
+    return out["wav"].clone()
+
+
+@register_fake("stzs::synth_voices")
+def _(handle, tokens, zbank, ibank, src, w, cnt, noise, durations, steps, cfg_scale, seeds):
+    n = torch.library.get_ctx().new_dynamic_size()
+    return tokens.new_empty((tokens.shape[0], n), dtype=torch.float32)
+
+
+@custom_op("stzs::voice_prompt", mutates_args=(), device_types="cuda")
+def voice_prompt(handle: int, zbank: torch.Tensor, ibank: Optional[torch.Tensor], src: torch.Tensor, w: torch.Tensor,
+                 cnt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """enrolled voices: zbank fp32 [V, L_s, code], src int32 [B, Kmax] voice ids, w fp32 [B, Kmax]
+    weights, cnt int32 [B] sources per row -> (indices int32 [B, L_s, G], dequantised codes fp32 [B, L_s, code]).
+    ibank (int32 [V, L_s, G], the voices' stored indices) given: the gather form -- every row is voice src[b, 0] at
+    weight 1, w and cnt are not read; None: the mix form, the product VQ of sum_k w[b, k] z[src[b, k]]."""
+    eng = _eng(handle, zbank, ibank, src, w, cnt)
+    S = eng.spec
+    G = S.code_dim // S.vq_group
+    V, Lr, D = zbank.shape
+    B = src.shape[0]
+    if (Lr, D) != (S.L_s, S.code_dim) or src.dim() != 2 or tuple(w.shape) != tuple(src.shape) or \
+            tuple(cnt.shape) != (B,) or (ibank is not None and tuple(ibank.shape) != (V, Lr, G)):
+        raise RuntimeError("stzs::voice_prompt: zbank [V, L_s, code], ibank [V, L_s, G], src / w [B, Kmax], cnt [B]")
+    idx = torch.empty(B, Lr, G, dtype=torch.int32, device=zbank.device)
+    out = torch.empty(B, Lr, D, dtype=torch.float32, device=zbank.device)
+    eng.voice_prompt(zbank.float().contiguous(), None if ibank is None else ibank.to(torch.int32).contiguous(),
+                     src.to(torch.int32).contiguous(), w.float().contiguous(), cnt.to(torch.int32).contiguous(), idx, out,
+                     gather=ibank is not None)
+    return idx, out
+
+
+@register_fake("stzs::voice_prompt")
+def _(handle, zbank, ibank, src, w, cnt):
+    G = zbank.shape[2] // _spec(handle).vq_group
+    B = src.shape[0]
+    return (zbank.new_empty((B, zbank.shape[1], G), dtype=torch.int32),
+            zbank.new_empty((B, zbank.shape[1], zbank.shape[2]), dtype=torch.float32))
+
+
 # ------------------------------------------------------------------ no engine handle
 @custom_op("stzs::resample", mutates_args=(), device_types="cuda")
 def resample(x: torch.Tensor, sr_in: int, sr_out: int, lens: Optional[torch.Tensor] = None,
@@ -487,4 +542,4 @@ def _(x, sr_in, sr_out, lens=None, pcm16=False):
 
 OPS = ["synth", "sample_style", "predict_prosody", "decode", "duration_head", "length_regulate",
        "cfg_euler_step", "istft", "istft_stream", "bilstm", "denoiser_fwd", "f0n_predictor", "decoder_pre",
-       "sine_gen", "conv_transpose_up", "mrf_resblock", "conv_post_istft", "code_quantize", "resample"]
+       "sine_gen", "conv_transpose_up", "mrf_resblock", "conv_post_istft", "code_quantize", "voice_prompt", "synth_voices", "resample"]

@@ -54,11 +54,19 @@ and converted in ONE ragged launch (the engine's resample(lens=...): row b the b
 request goes on with its own-length reference at the model's rate, so the grouping keys see those lengths.  After phase
 2 the waveforms of each distinct foreign out_sr are converted the same way.  stats["resample_batches"] counts both; a
 list of requests at the defaults makes, call for call, the calls from before.
+
+Enrolled voices: a Request may name its speaker as a Voice (engine.enroll), or as a blend -- a sequence
+of (Voice, weight) pairs -- in place of ref_wav.  Such requests have no reference length: their phase-1 key holds a
+constant in its place, whatever the flags, so they batch together and never with waveform requests.  Per chunk the
+distinct Voice objects (by identity, in first-appearance order) are stacked into one bank, ONE VoiceRows is made and the
+prompt is ONE stzs_voice_prompt launch: data movement only, as the regrouping.  stats["voice_batches"] counts those
+chunks; a list without voices makes, call for call, the calls from before.
 """
 from __future__ import annotations
 
 import dataclasses
 import time
+from functools import partial
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import List, Optional
@@ -66,13 +74,14 @@ from typing import List, Optional
 import torch
 
 from . import resample as RS
+from . import voice as VC
 from .engine import Act, StyleTTSZS
 
 
 @dataclass
 class Request:
     tokens: torch.Tensor            # int [T_txt]
-    ref_wav: torch.Tensor           # fp32 [N] reference (at 24 kHz, or at ref_sr)
+    ref_wav: Optional[torch.Tensor]  # fp32 [N] reference (at 24 kHz, or at ref_sr); None with `voice`
     noise: torch.Tensor             # fp32 [L_s, code_dim] style noise
     seed: int = 0                   # harmonic-source noise seed
     durations: Optional[torch.Tensor] = None  # optional forced int [T_txt]
@@ -81,13 +90,36 @@ class Request:
     pitch_shift: float = 0.0        # semitones: F0 is multiplied by 2 ** (pitch_shift / 12)
     ref_sr: Optional[int] = None    # the rate of ref_wav (None: the model's 24 kHz)
     out_sr: Optional[int] = None    # the rate of the returned waveform (None: the model's)
+    voice: object = None            # an enrolled Voice, or a sequence of (Voice, weight) pairs (a blend): no ref_wav
+
+
+def request_voices(r):
+    """the (Voice, weight) pairs of a request's `voice` field -> ([Voice], [weight] | None); None for a waveform
+    request.  ValueError for a request with both a voice and a reference (or a ref_sr), with neither, for a blend that
+    is empty or holds something else than (Voice, weight) pairs."""
+    v = getattr(r, "voice", None)
+    if v is None:
+        if r.ref_wav is None:
+            raise ValueError("Request: neither ref_wav nor voice is given")
+        return None
+    if r.ref_wav is not None or getattr(r, "ref_sr", None) is not None:
+        raise ValueError("Request: voice and ref_wav / ref_sr were both given: the speaker comes from one or the other")
+    if isinstance(v, VC.Voice):
+        return [v], None
+    try:
+        pairs = [(a, float(b)) for a, b in v]
+    except (TypeError, ValueError):
+        raise ValueError("Request.voice must be a Voice or a sequence of (Voice, weight) pairs")
+    if not pairs or any(not isinstance(a, VC.Voice) for a, _ in pairs):
+        raise ValueError("Request.voice must be a Voice or a sequence of (Voice, weight) pairs")
+    return [a for a, _ in pairs], [b for _, b in pairs]
 
 
 class Stats(dict):
     """BucketScheduler.stats.  A counter that came with a per-request option and is zero for a list of requests that
     does not use the option is not listed -- the statistics of such a list are, key for key, the ones from before the
     option -- and reads as 0."""
-    OPTIONAL = ("resample_batches",)
+    OPTIONAL = ("resample_batches", "voice_batches")
 
     def __missing__(self, key):
         if key in self.OPTIONAL:
@@ -117,12 +149,15 @@ class BucketScheduler:
     def phase1_groups(self, reqs: List[Request]):
         """the phase-1 batches of reqs, in launch order -> [(forced durations?, [request indices])], each of at most
         max_batch requests that share (token count, reference length, forced); ragged_text takes the token count out
-        of the key, ragged_ref the reference length (both: (forced,) alone).  Pure host bookkeeping (reads shapes
-        only)."""
+        of the key, ragged_ref the reference length (both: (forced,) alone).  A request that names an enrolled voice has
+        the constant "voice" where the reference length stands, whatever ragged_ref says: voice requests share batches
+        among themselves and never with waveform requests.  Pure host bookkeeping (reads shapes only)."""
         g1 = OrderedDict()
         for i, r in enumerate(reqs):
             key = (r.durations is not None,)
-            if not self.ragged_ref:
+            if request_voices(r) is not None:
+                key = ("voice",) + key
+            elif not self.ragged_ref:
                 key = (int(r.ref_wav.shape[0]),) + key
             if not self.ragged_text:
                 key = (int(r.tokens.shape[0]),) + key
@@ -167,6 +202,21 @@ class BucketScheduler:
             for j, i in enumerate(ids):
                 done[i] = y[j, :RS.out_len(nl[j], *RS.ratio(a, b))].clone()
         return done
+
+    def _voice_rows(self, items):
+        """the speakers of one phase-1 chunk: items [([Voice], [weight] | None)] per request -> VoiceRows over a bank
+        stacked from the chunk's distinct Voice objects (by identity, in first-appearance order).  Data movement only."""
+        order, pos = [], {}
+        for vs, _ in items:
+            for v in vs:
+                if id(v) not in pos:
+                    VC._check_voice(v, self.eng, "Request.voice")
+                    pos[id(v)] = len(order)
+                    order.append(v)
+        ids = [[pos[id(v)] for v in vs] for vs, _ in items]
+        if all(len(r) == 1 for r in ids):
+            return self.eng.voice_rows(len(items), VC._Stack(order), [r[0] for r in ids])
+        return self.eng.voice_rows(len(items), VC._Stack(order), ids, [ws for _, ws in items])
 
     def _phase1_controls(self, reqs, ch):
         """the guidance / rate controls of phase-1 chunk ch -> RowControls, or None when every request of it is at the
@@ -255,17 +305,20 @@ class BucketScheduler:
         eng, S, dev = self.eng, self.eng.spec, self.eng.device
         self._nrs = 0  # ragged sample-rate conversions
         out_srs = [getattr(r, "out_sr", None) for r in reqs]
-        refs = self._resample_groups({i: r.ref_wav for i, r in enumerate(reqs)},
+        voiced = [request_voices(r) for r in reqs]  # (checks every request before anything is launched)
+        refs = self._resample_groups({i: r.ref_wav for i, r in enumerate(reqs) if voiced[i] is None},
                                      lambda i: getattr(reqs[i], "ref_sr", None), True)
         if refs:  # the requests go on with their references at the model's rate (the caller's are left as they are);
             # the converted ones live on the device, so the others of the list are taken there too: one batch stacks both
-            reqs = [dataclasses.replace(r, ref_wav=refs[i] if i in refs else r.ref_wav.to(dev), ref_sr=None)
+            reqs = [r if voiced[i] is not None else
+                    dataclasses.replace(r, ref_wav=refs[i] if i in refs else r.ref_wav.to(dev), ref_sr=None)
                     for i, r in enumerate(reqs)]
         # ---- phase 1: text / prompt / style / durations, grouped by (T_txt, N_ref) -- ragged_text: without T_txt,
         # ragged_ref: without N_ref ----
         per = [None] * len(reqs)
         n1 = 0
         self._nctl = 0  # batches that ran with controls
+        nvoice = 0  # phase-1 batches whose prompt came from enrolled voices
         ref_n = pad_n = 0  # reference samples of the phase-1 blocks, and how many of them are padding
         t1 = time.perf_counter()  # (every phase-1 batch ends in a host sync: the wall time is the phase's)
         for forced, ch in self.phase1_groups(reqs):
@@ -283,10 +336,14 @@ class BucketScheduler:
             else:
                 tok = torch.stack([reqs[i].tokens for i in ch]).to(dev, torch.int32)
                 dur_ov = torch.stack([reqs[i].durations for i in ch]) if forced else None
-            nl = [int(reqs[i].ref_wav.shape[0]) for i in ch]
+            vr = ref = rlens = None
+            # (a chunk is all voices or all waveforms: the key keeps them apart; voices have no reference samples)
+            nl = [0] if voiced[ch[0]] is not None else [int(reqs[i].ref_wav.shape[0]) for i in ch]
             Nm = max(nl)
-            rlens = None
-            if self.ragged_ref and min(nl) < Nm:
+            if voiced[ch[0]] is not None:
+                vr = self._voice_rows([voiced[i] for i in ch])
+                nvoice += 1
+            elif self.ragged_ref and min(nl) < Nm:
                 # pad to the chunk's longest reference (zeros: never read) and hand the rows' own sample counts down
                 ref = torch.stack([torch.nn.functional.pad(reqs[i].ref_wav, (0, Nm - reqs[i].ref_wav.shape[0]))
                                    for i in ch]).to(dev, torch.float32)
@@ -296,21 +353,23 @@ class BucketScheduler:
                 ref = torch.stack([reqs[i].ref_wav for i in ch]).to(dev, torch.float32)
             ref_n += Nm * len(ch)
             eps = torch.stack([reqs[i].noise for i in ch]).to(dev, torch.float32)
+            # the prompt of the chunk: the front end on its references, or one launch on its enrolled voices
+            prompt_of = (lambda **kw: eng.voice_encode(vr)) if vr is not None else partial(eng.prompt_encode, ref)
             rc = self._phase1_controls(reqs, ch)
             if rc is not None:
                 self._nctl += 1
                 h = eng.text_encode(tok, lens)
-                prompt = eng.prompt_encode(ref, ref_lens=rlens)
+                prompt = prompt_of(ref_lens=rlens)
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg, lens, controls=rc)
                 du = eng.predict_durations(h, codes, dur_ov, lens, controls=rc)
             elif lens is None and rlens is None:  # (the uniform path, call for call as before)
                 h = eng.text_encode(tok)
-                prompt = eng.prompt_encode(ref)
+                prompt = prompt_of()
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg)
                 du = eng.predict_durations(h, codes, dur_ov)
             else:
                 h = eng.text_encode(tok, lens)
-                prompt = eng.prompt_encode(ref, ref_lens=rlens)
+                prompt = prompt_of(ref_lens=rlens)
                 codes = eng.sample_style(h, prompt, eps, self.steps, self.cfg, lens)
                 du = eng.predict_durations(h, codes, dur_ov, lens)
             tot = du["dur"].to(torch.int64).sum(1).cpu()  # host sync: frame counts decide phase 2
@@ -364,4 +423,6 @@ class BucketScheduler:
                           decoder_batches=n2, decoder_pad_share=fpad_n / max(fr_n, 1) if self.ragged_decoder else 0.0)
         if self._nrs:  # (the ragged sample-rate conversions, both directions; reads as 0 where it is not listed)
             self.stats["resample_batches"] = self._nrs
+        if nvoice:  # (likewise)
+            self.stats["voice_batches"] = nvoice
         return out
